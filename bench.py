@@ -9,9 +9,14 @@ Workload: Graph500-style R-MAT scale 26, edgefactor 16 (1,073,741,824 records), 
 the metric's config (BASELINE.json configs[3]); it fits one GPU, so N=1 runs it whole and
 N>1 shards the same records across ranks (strong scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scale S] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scale S] [--dump-outputs DIR] [--full]
 N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the CPU
+baselines (cpu_baseline, cpu_baseline_ir; --no-cpu-baseline leaves them out again).
+--dump-outputs DIR writes what the last timed step returned (seq, parent, pst, n_seq) as
+DIR/<name>.npy: the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -117,7 +122,15 @@ def parse_args(argv=None):
     ap.add_argument("--edgefactor", type=int, default=16)
     ap.add_argument("--seed", type=int, default=26)
     ap.add_argument("--cpu-scale", type=int, default=22)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baselines (cpu_baseline, cpu_baseline_ir) on an "
+                         "R-MAT --cpu-scale sample; a plain run only times the GPU steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baselines out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's seq / parent / pst (a fixed seeded sample "
+                         "of the n_seq valid entries when they are many) and n_seq as "
+                         "DIR/<name>.npy, float64")
     ap.add_argument("--check", action="store_true", help="verify the tree against the CPU checker")
     # rehearsal of the N > 1 path on a one-GPU box (every rank on cuda:0, gloo carrying device
     # tensors: RCCL refuses two ranks on one device); timings are then meaningless
@@ -190,8 +203,37 @@ def join_comm(rank, world, dev):
     return uid[0]
 
 
+DUMP_SAMPLE = 1 << 20  # entries kept per array: 3 arrays + their index, 8 B each = 32 MiB
+DUMP_SEED = 20260  # of the sample's positions
+
+
+def dump_outputs(path, out):
+    """Write what a caller of the timed step receives, (seq, parent, pst, n_seq), as float64
+    `path`/<name>.npy (u32 values are exact there).  Only the n_seq valid entries count (the
+    buffers hold n_ids slots); above DUMP_SAMPLE of them, the same seeded sorted positions of
+    every array are kept and written beside them as sample_index.npy."""
+    import numpy as np
+
+    seq, parent, pst, n_seq = out[0], out[1], out[2], int(out[3])
+    os.makedirs(path, exist_ok=True)
+    idx = None
+    if n_seq > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n_seq, DUMP_SAMPLE))
+        idx = torch.from_numpy(pos).to(seq.device)
+        np.save(os.path.join(path, "sample_index.npy"), pos.astype(np.float64))
+    for name, t in (("seq", seq), ("parent", parent), ("pst", pst)):
+        v = t[:n_seq].view(torch.int32)
+        if idx is not None:
+            v = v.index_select(0, idx)
+        np.save(os.path.join(path, name + ".npy"),
+                v.cpu().numpy().view(np.uint32).astype(np.float64))
+    np.save(os.path.join(path, "n_seq.npy"), np.array([n_seq], np.float64))
+
+
 def main():
     args = parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     world, rank, local = rank_env(args.gpus)
     if args.same_device:
         local = 0
@@ -255,6 +297,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         n_seq = out[3] if world > 1 else out[3]
@@ -325,7 +369,7 @@ def main():
         if args.check:
             rec["check"] = check_tree(out, uv if world == 1 else None, scale, ef, seed,
                                       args.workload)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(args.cpu_scale, ef, args.cpu_scale)
             # `mpirun -n <cores>`: the cores this job may use — its cgroup CPU quota (the GPU
             # box: cpu.max 1600000/100000 = 16 of the host's 256 logical CPUs); more ranks than

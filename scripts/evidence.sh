@@ -8,7 +8,7 @@ set -o pipefail
 OUT=${OUT:-gpurun_out/ev}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 400 python bench.py > "$OUT/bench_rmat26.json" 2> "$OUT/bench.err" && echo "bench ok" &&
+timeout -k 10 400 python bench.py --full > "$OUT/bench_rmat26.json" 2> "$OUT/bench.err" && echo "bench ok" &&
 timeout -k 10 200 python bench.py --workload lj --no-cpu-baseline > "$OUT/bench_lj.json" 2>> "$OUT/bench.err" && echo "lj ok" &&
 timeout -k 10 200 python bench.py --workload twitter --no-cpu-baseline > "$OUT/bench_twitter.json" 2>> "$OUT/bench.err" && echo "tw ok" &&
 timeout -k 10 200 python bench.py --scale 22 --seed 22 --no-cpu-baseline --check > "$OUT/bench_rmat22_checked.json" 2>> "$OUT/bench.err" && echo "rmat22 ok" &&

@@ -5,5 +5,5 @@ timeout -k 10 500 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -2 $O/pytest.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 echo bench ok
