@@ -50,8 +50,6 @@ static const KnobDef kKnobs[] = {
 };
 
 static Knobs g_knobs;
-// the fused front pass's tile groups (Knobs::ff_groups), clamped to 1..8
-static uint32_t ff_groups();
 static std::once_flag g_knobs_once;
 
 static void load_knobs_from_env() {
@@ -72,6 +70,8 @@ Knobs& knobs() {
   return g_knobs;
 }
 
+// the fused front pass's tile groups (Knobs::ff_groups), clamped to 1..8: read once per call, by
+// front_half
 static uint32_t ff_groups() { return (uint32_t)std::max(1, std::min(8, knobs().ff_groups)); }
 
 struct HipError : std::runtime_error {
@@ -386,22 +386,35 @@ static bool degree_dev(Ctx& c, const uint32_t* d_uv, uint64_t m, uint32_t n_ids,
                                 counted, stats);
 }
 
-// Optional degree information for pst without per-edge atomics (launch_pst_from_degree).
+// Degree information of the records at hand: pst without per-edge atomics
+// (launch_pst_from_count) and the hi bins' estimate.
 struct DegInfo {
   const uint32_t* seq = nullptr;    // jnid -> vid
   const uint32_t* deg = nullptr;    // degrees of THESE records
   const uint32_t* selfc = nullptr;  // self-loop records per vid
   int mode = SHEEP_DEGREE_LLAMA;
-  bool yhist_ready = false;         // degree_dev counted the partition's y digits (part_ws)
   const uint32_t* nsd = nullptr;    // rank-ordered deg - w * selfc (nullable, see sequence_dev)
-  bool part_first_done = false;     // the first partition pass was launched on c.side into
-                                    // e_items; c.part_ev[1] marks its end
-  uint64_t mid_slots = 0;           // ... of which e_items holds this many (0: m)
-  bool mid_caps = false;            // ... into capacity regions (launch_part_first_caps): its
-                                    // overflow word is c.d_err[3]
-  bool mid_p6 = false;              // ... packed by the fused front pass (launch_front_fused)
-  bool ids_checked = false;         // an id >= n_rank fails the call anyway (the degree pass's
-                                    // ERR_RANGE): the partition passes may pack (part_p6_ok)
+};
+
+// What the front half (front_half) leaves for the regrouping by hi bin (bin_records).
+struct Front {
+  hipEvent_t part_done = nullptr;  // the first partition pass of the rank gathers was launched
+                                   // into the caller's items slot ("part_ws" holding its
+                                   // cursors) and completes at this event (null: not launched)
+  uint64_t mid_slots = 0;          // ... the records the items slot then holds
+  bool mid_caps = false;           // ... in capacity regions (launch_part_first_caps,
+                                   // launch_front_fused): their overflow word is c.d_err[3]
+  bool mid_p6 = false;             // ... packed by the fused front pass (launch_front_fused)
+  uint32_t G = 1;                  // ... in this many tile groups (the option ff_groups as the
+                                   // first pass read it: the second pass must use the same)
+  bool fused = false;              // the degree pass itself wrote those records (on the working
+                                   // stream): an id out of range leaves them short
+  bool yhist_ready = false;        // no first pass yet, but the degree pass counted its y digits
+                                   // into "part_ws"
+  bool ids_checked = false;        // an id >= n_rank fails the call anyway (the degree pass's
+                                   // ERR_RANGE): the partition passes may pack (part_p6_ok)
+  bool stats_host = false;         // the degree stats are already in c.h_pinned[0..2]
+  bool err_range = false;          // the pass's readback saw ERR_RANGE (the device word stays set)
 };
 
 // Rank gathers in partitioned order (launch_part_gather) for large inputs.
@@ -447,6 +460,141 @@ static uint32_t sequence_dev(Ctx& c, const uint32_t* d_deg, uint32_t n_ids, uint
     launch_unpack_seq(sorted, 0, n_big, d_seq, d_rank, s, nsd, sc, mode, base);
   }
   return n_seq;
+}
+
+// ---- the front half of a graph2tree, for both drivers ------------------------
+// The degrees of these records and the first partition pass of their rank gathers (which needs
+// no ranks, only the records), in one of five variants decided here, once:
+//   sampled-fused (part_overlap 4, from 2^25 records): ONE read of the records for both, packed
+//     first-pass records in sampled capacity regions (launch_front_fused);
+//   counted-fused (3; always past 2^31 records, where the endpoint offsets of the unfused degree
+//     pass end): the degree pass writes the records grouped by y bucket (launch_fh_front);
+//   sampled (2, from 2^25 records): no counting read — the degree scatter and the first pass,
+//     beside it on the side stream, write capacity regions sized from a 1/256 sample;
+//   beside (2: once the degree pass has counted the y digits; 1: after the whole degree pass):
+//     the first pass on the side stream, beside the sequence (and the degree collectives);
+//   in line (0, or no partitioned gathers): the degree pass alone.
+// 4 below its size or with ids it cannot take is 2.  A sampled region that overflows sends the
+// degrees through the exact pass here (a local decision: no collectives), the partition through
+// bin_records' fallback.  The mid records go to the slot `items_slot` of c.scratch, at least m
+// u64 so that the tree build, which takes the same buffer at that size, does not regrow it.
+// want_stats: the exact and unfused passes also leave the degree stats in "stats" (the fused and
+// sampled ones always do).  A range error is reported (err_range), never thrown: a rank of a
+// group must carry it through the degree collectives to check_err_group.
+static Front front_half(Ctx& c, const char* items_slot, const uint32_t* d_uv, uint64_t m,
+                        uint32_t n_ids, int mode, uint32_t* deg, uint32_t* selfc, bool want_stats,
+                        hipStream_t s, Timer* tm) {
+  Front f;
+  f.ids_checked = true;
+  f.G = ff_groups();
+  int ov = knobs().part_overlap;
+  const bool part = m > 0 && use_part(m);
+  const bool bucketed = knobs().degree != 1;
+  const bool caps_ok = bucketed && m >= (1ull << 25) && knobs().bin_direct && part_p6_ok(n_ids) &&
+                       degs_tmp_words(m, n_ids) > 1;
+  enum { IN_LINE, BESIDE, SAMPLED, COUNTED_FUSED, SAMPLED_FUSED } v = IN_LINE;
+  if (part && bucketed && n_ids > 0 && (ov == 3 || 2 * m >= (1ull << 32)) &&
+      fh_tmp_words(m, n_ids) > 1) {
+    v = COUNTED_FUSED;
+  } else if (part && ov == 4 && caps_ok && front_fused_ok(m, n_ids)) {
+    v = SAMPLED_FUSED;
+  } else if (part && ov != 0) {
+    if (ov == 4) ov = 2;
+    v = ov == 2 && caps_ok && 2 * m < (1ull << 32) ? SAMPLED : BESIDE;
+  }
+  uint32_t* stats = (uint32_t*)c.scratch.get("stats", 16);
+  // (the scratch slots are taken in one fixed order per variant: where the buffers of the first
+  // call land shapes the passes' times, DESIGN.md §9 "run-to-run spread")
+  auto part_ws = [&] { return (uint32_t*)c.scratch.get("part_ws", PART_WS_WORDS * 4); };
+  auto mid_buf = [&](uint64_t slots) {
+    f.mid_slots = slots;
+    return (uint64_t*)c.scratch.get(items_slot, std::max<uint64_t>(m, slots) * 8);
+  };
+  void (*const mark)(void*, const char*) =
+      tm ? +[](void* t, const char* n) { ((Timer*)t)->mark(n); } : nullptr;
+  auto exact = [&]() {  // a region outgrew its capacity: the degrees again, counted
+    degree_dev(c, d_uv, m, n_ids, mode, deg, selfc, s, false, nullptr, want_stats ? stats : nullptr);
+    if (tm) tm->mark("degree_exact");
+    f.stats_host = false;
+  };
+  auto first_beside = [&](auto launch) {  // k_part<0> on the side stream, live-timed for bench
+    HIP_CHECK(hipStreamWaitEvent(c.side, c.part_ev[0], 0));
+    const size_t sp = tm ? tm->span_begin("part_first", c.side) : 0;
+    launch();
+    if (tm) tm->span_end(sp, c.side);
+    HIP_CHECK(hipEventRecord(c.part_ev[1], c.side));
+    f.part_done = c.part_ev[1];
+  };
+  uint32_t* const ovf_deg = c.d_err + 2;   // ([2] the degrees' overflow word, [3] the partition's)
+  uint32_t* const ovf_part = c.d_err + 3;
+  if (v == COUNTED_FUSED) {
+    require_records(m, "degree");  // its offsets count records, not endpoints
+    uint32_t* tmp = (uint32_t*)c.scratch.get("degb_tmp", fh_tmp_words(m, n_ids) * 4);
+    uint64_t* mid = mid_buf(m);
+    launch_fh_front(d_uv, m, n_ids, mode, deg, selfc, c.d_err, tmp, mid, part_ws(), stats, s, mark,
+                    tm);
+    if (tm) tm->mark("degree_hist");
+    HIP_CHECK(hipEventRecord(c.part_ev[1], s));
+    f.part_done = c.part_ev[1];
+    f.fused = true;
+  } else if (v == SAMPLED_FUSED) {
+    HIP_CHECK(hipMemsetAsync(ovf_deg, 0, 8, s));  // both overflow words
+    uint32_t* tmp = (uint32_t*)c.scratch.get("degs_tmp", degs_tmp_words(m, n_ids) * 4);
+    uint32_t* pws = part_ws();
+    uint64_t* mid = mid_buf(front_fused_slots(m, n_ids, f.G));
+    launch_front_fused(d_uv, m, n_ids, mode, deg, selfc, c.d_err, tmp, pws, mid, f.mid_slots, stats,
+                       ovf_deg, ovf_part, s, mark, tm, f.G);
+    if (tm) tm->mark("degree_hist");
+    HIP_CHECK(hipEventRecord(c.part_ev[1], s));
+    f.part_done = c.part_ev[1];
+    f.fused = f.mid_caps = f.mid_p6 = true;
+    // One readback: the error word and both overflow words (d_err[0..3]) with the degree stats.
+    // The degrees are complete unless a region outgrew its capacity: an x bucket, or a y digit
+    // (the histogram counts y's ids from the packed records, which then lost the run's tail);
+    // an id out of range leaves the pass's record array short, which is reported here, before
+    // anything reads it (the check_err the sequence would otherwise need).
+    HIP_CHECK(hipMemcpyAsync(c.h_pinned + 4, c.d_err, 16, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(c.h_pinned, stats, 12, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    f.stats_host = true;
+    f.err_range = (c.h_pinned[4] & ERR_RANGE) != 0;
+    // (not after a range error: the call fails, and the exact pass would raise the word again
+    // after the caller has reset it)
+    if (!f.err_range && (c.h_pinned[6] || c.h_pinned[7])) exact();
+  } else if (v == SAMPLED) {
+    HIP_CHECK(hipEventRecord(c.part_ev[0], s));
+    HIP_CHECK(hipMemsetAsync(ovf_deg, 0, 8, s));  // both overflow words
+    uint32_t* tmp = (uint32_t*)c.scratch.get("degs_tmp", degs_tmp_words(m, n_ids) * 4);
+    uint32_t* pws = part_ws();
+    uint64_t* mid = mid_buf((fs_room(m, 1024) + 7) & ~7ull);
+    launch_degree_sampled(d_uv, m, n_ids, mode, deg, selfc, c.d_err, tmp, pws, f.mid_slots, stats,
+                          ovf_deg, s, c.part_ev[0]);
+    if (tm) tm->mark("degree");
+    first_beside([&] {
+      launch_part_first_caps(d_uv, m, n_ids, mid, f.mid_slots, pws, ovf_part, c.side);
+    });
+    f.mid_caps = true;
+    // the degrees are complete and valid unless a bucket outgrew its region (the stream syncs
+    // here once; the sequence would wait for the degree pass anyway)
+    HIP_CHECK(hipMemcpyAsync(c.h_pinned + 4, ovf_deg, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (c.h_pinned[4]) exact();
+  } else {
+    const bool beside = v == BESIDE;
+    if (beside) HIP_CHECK(hipEventRecord(c.part_ev[0], s));  // in case degree_dev records none
+    f.yhist_ready = degree_dev(c, d_uv, m, n_ids, mode, deg, selfc, s, part,
+                               beside && ov == 2 ? c.part_ev[0] : nullptr,
+                               want_stats ? stats : nullptr);
+    if (tm) tm->mark("degree");
+    if (beside) {
+      uint64_t* mid = mid_buf(m);
+      uint32_t* pws = part_ws();
+      if (ov != 2) HIP_CHECK(hipEventRecord(c.part_ev[0], s));
+      first_beside([&] { launch_part_first(d_uv, m, n_ids, mid, pws, c.side, f.yhist_ready); });
+      f.yhist_ready = false;  // (consumed)
+    }
+  }
+  return f;
 }
 
 // Liu's elimination tree from items sorted by hi down to groups of 2^lo_bit ranks (m items,
@@ -857,12 +1005,192 @@ static Buckets buckets_from_bins(const std::vector<uint32_t>& bounds,
   return bk;
 }
 
-// allow_direct: the hi bins may be filled directly by the edge pass (launch_edge_bin); false
-// after a bin outgrew its estimate (the records are then grouped by the scatter).
+// ---- the regrouping of a shard's records by hi bin, for both drivers ------------------------
+// The rank gathers' partition: the records as (x, rank[y]) in x-digit order in items_b — the
+// second pass over the front half's first-pass records where it ran (f->part_done), else both
+// passes from the records.  p6: the output packed to 6 bytes (launch_edge_bin alone reads that).
+static void part_records(const uint32_t* d_uv, uint64_t m, const uint32_t* d_rank, uint32_t n_rank,
+                         uint64_t* items, uint64_t* items_b, uint32_t* pws, const Front* f,
+                         bool p6, hipStream_t s) {
+  if (f && f->part_done) {  // pass 1 ran beside the sequence (and the degree collectives)
+    HIP_CHECK(hipStreamWaitEvent(s, f->part_done, 0));
+    launch_part_second(items, m, d_rank, n_rank, items_b, pws, s, p6, f->mid_slots, f->mid_caps,
+                       f->mid_p6, f->G);
+  } else {
+    launch_part_gather(d_uv, m, d_rank, n_rank, items, items_b, pws, s, f && f->yhist_ready, p6);
+  }
+}
+
+// The overflow word of the first pass's capacity regions, where nothing else reads it back (no
+// direct binning): an overflowed region lost records, and the partition is then run again from
+// the records.  Synchronises s.
+static bool mid_overflowed(Ctx& c, hipStream_t s) {
+  HIP_CHECK(hipMemcpyAsync(c.h_pinned + 10, c.d_err + 3, 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  return c.h_pinned[10] != 0;
+}
+
+// The scratch slots of bin_records, per caller: the tree build's are shared with the other
+// one-call entry points, a lockstep session keeps its own across API calls.
+struct BinSlots {
+  const char *items, *items_b, *rsort_tmp, *item_bins, *chunk_deg, *bins, *bin_segs, *binned,
+      *bin_start;
+};
+static const BinSlots kTreeSlots = {"e_items",   "e_items_b", "rsort_tmp", "item_bins", "chunk_deg",
+                                    "hi_bins",   "bin_segs",  "e_binned",  "bin_start"};
+static const BinSlots kLsSlots = {"ls_items",     "ls_items_b", "ls_rsort_tmp",
+                                  "ls_item_bins", "ls_chunk_deg", "ls_bins",
+                                  "ls_bin_segs",  "ls_binned",  "ls_bin_start"};
+
+// Items (hi << 32 | lo) grouped by hi bin.
+struct Binned {
+  bool direct = false;             // filled directly by the edge pass (launch_edge_bin): bin i's
+                                   // items at [start[i], its cursor), the INVALID bin not stored
+  const uint64_t* sorted = nullptr;
+  uint64_t* spare = nullptr;       // m free u64
+  std::vector<uint32_t> bounds;    // the hi bins (make_bins), on the device at d_bins
+  uint32_t* d_bins = nullptr;
+  // direct: the capacity start of each bin, then the end (nb entries); else the nb + 1 record
+  // offsets of the scatter
+  std::vector<unsigned long long> start;
+  unsigned long long* dseg = nullptr;  // direct: start | cursor | capacity end, 512 u64 each
+  std::vector<uint64_t> counts;        // the records of each bin, for the caller that asks
+};
+
+// m > 0 records (or a lockstep rank's empty shard) -> items grouped by the hi bins cut from the
+// degrees (seq, deg, nsd as launch_chunk_degsum; n_seq > 0).  f: what the front half left.
+// shard: the degrees are global and the records one rank's, so a bin's capacity is this shard's
+// share of its estimate (share = 1 for the whole graph).  The bin sums reach the host BEFORE the
+// partition pass is enqueued: the host cuts the bins while the GPU runs that pass.
+// Direct binning (the option bin_direct) fills capacity regions sized by the estimate; a bin
+// that outgrows its region, or an overflowed region of the first partition pass, sends the
+// records through the scatter (group_by_bins) — from the unpacked records, partitioned again
+// where they were packed or incomplete.  Without want_counts nothing but the overflow words is
+// read back: the caller cuts its buckets on the estimates, and on the scatter path while the
+// scatter runs (c.h_bstart / c.bins_ev).
+static Binned bin_records(Ctx& c, Scratch& sc, const BinSlots& nm, const uint32_t* d_uv, uint64_t m,
+                          const uint32_t* d_rank, uint32_t n_rank, const uint32_t* d_seq,
+                          const uint32_t* d_deg, const uint32_t* nsd, uint32_t n_seq,
+                          const Front& f, bool shard, bool want_counts, hipStream_t s, Timer* tm) {
+  Binned r;
+  const size_t nch = ((size_t)n_seq + 255) / 256;
+  uint64_t* cds = (uint64_t*)sc.get(nm.chunk_deg, nch * 8);
+  launch_chunk_degsum(d_seq, d_deg, n_seq, cds, s, nsd);
+  if (c.h_chunks_n < nch) {
+    if (c.h_chunks) HIP_CHECK(hipHostFree(c.h_chunks));
+    c.h_chunks = nullptr;
+    c.h_chunks_n = 0;
+    HIP_CHECK(hipHostMalloc((void**)&c.h_chunks, nch * 8, hipHostMallocDefault));
+    c.h_chunks_n = nch;
+  }
+  HIP_CHECK(hipMemcpyAsync(c.h_chunks, cds, nch * 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipEventRecord(c.bins_ev, s));
+  const uint64_t mm = std::max<uint64_t>(m, 1);
+  uint64_t* items = (uint64_t*)sc.get(nm.items, mm * 8);
+  uint64_t* items_b = (uint64_t*)sc.get(nm.items_b, mm * 8);
+  uint32_t* tmp = (uint32_t*)sc.get(nm.rsort_tmp, rsort_tmp_words(mm) * 4);
+  const bool part = m > 0 && use_part(m);
+  const bool direct = knobs().bin_direct && m > 0;
+  // The second pass's records packed to 6 bytes: only the direct edge pass reads them, and its
+  // tile descriptors sit in the spare 2 bytes per record behind them, which hold them from 2^20
+  // records (ids_checked: an id >= n_rank fails the call anyway).
+  const bool pre6 = part && direct && f.ids_checked && part_p6_ok(n_rank) && m >= (1ull << 20);
+  const bool mid_caps = part && f.part_done && f.mid_caps;
+  uint32_t* pws = part ? (uint32_t*)sc.get("part_ws", PART_WS_WORDS * 4) : nullptr;
+  const uint32_t* src = d_uv;
+  if (part) {
+    part_records(d_uv, m, d_rank, n_rank, items, items_b, pws, &f, pre6, s);
+    src = (const uint32_t*)items_b;
+    if (tm) tm->mark("partition");
+  }
+  HIP_CHECK(hipEventSynchronize(c.bins_ev));
+  std::vector<uint64_t> hd(c.h_chunks, c.h_chunks + nch);
+  std::vector<double> est;
+  r.bounds = make_bins(hd, n_seq, &est);
+  const uint32_t nb = (uint32_t)r.bounds.size();
+  r.d_bins = (uint32_t*)sc.get(nm.bins, 512 * 4);
+  HIP_CHECK(hipMemcpyAsync(r.d_bins, r.bounds.data(), nb * 4, hipMemcpyHostToDevice, s));
+  bool repart = pre6;  // the scatter reads unpacked records
+  if (direct) {
+    // Each bin gets a capacity region sized by its estimated records (+ slack); the edge pass
+    // fills them directly, and the buckets are cut on the estimate (any cuts are exact).
+    double share = 1.0;
+    if (shard) {
+      double W = 0;
+      for (double e : est) W += e;
+      if (W > 0) share = std::min(1.0, (double)m / W);
+    }
+    const double slack = 1.0 + knobs().bin_slack / 1000.0;
+    r.start.assign(nb, 0ull);
+    std::vector<unsigned long long> h(3 * 512, 0ull);  // start | cursor | capacity end
+    for (uint32_t i = 0; i + 1 < nb; ++i) {
+      // a bin never holds more than m items (and the map keeps segment lengths in u32)
+      const uint64_t cap =
+          std::min<uint64_t>((uint64_t)std::ceil(est[i] * share * slack) + 8192, m);
+      r.start[i + 1] = r.start[i] + cap;
+      h[i] = h[512 + i] = r.start[i];
+      h[1024 + i] = r.start[i + 1];
+    }
+    r.dseg = (unsigned long long*)sc.get(nm.bin_segs, h.size() * 8);
+    HIP_CHECK(hipMemcpyAsync(r.dseg, h.data(), h.size() * 8, hipMemcpyHostToDevice, s));
+    uint32_t* ovf = c.d_err + 1;  // a directly binned bin outgrew its capacity
+    HIP_CHECK(hipMemsetAsync(ovf, 0, 4, s));
+    uint64_t* binned = (uint64_t*)sc.get(nm.binned, std::max<uint64_t>(r.start[nb - 1], 1) * 8);
+    launch_edge_bin(src, part, m, d_rank, n_rank, c.d_err, r.d_bins, nb, r.dseg + 512,
+                    r.dseg + 1024, binned, ovf, s, pre6 ? pws : nullptr);
+    if (tm) tm->mark("edge_pass");
+    // One readback before the kb loop is enqueued (the host then enqueues while the GPU runs
+    // the first buckets): a bin that outgrew its estimate holds a hole where its dropped runs
+    // were reserved.  With ovf travels the first partition pass's overflow word, c.d_err[3].
+    std::vector<unsigned long long> cur(want_counts ? nb : 0);
+    if (want_counts)
+      HIP_CHECK(hipMemcpyAsync(cur.data(), r.dseg + 512, nb * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(c.h_pinned + 8, ovf, 12, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const bool part_ovf = mid_caps && c.h_pinned[10] != 0;
+    if (c.h_pinned[8] == 0 && !part_ovf) {
+      r.direct = true;
+      r.sorted = binned;
+      r.spare = items;  // free: held k_part's mid records (src is items_b or d_uv)
+      if (want_counts) {
+        r.counts.assign(nb, 0);  // (INVALID his, the last bin's, are not stored)
+        for (uint32_t i = 0; i + 1 < nb; ++i) r.counts[i] = cur[i] - r.start[i];
+      }
+      return r;
+    }
+    repart = repart || part_ovf;
+  } else if (mid_caps) {
+    repart = mid_overflowed(c, s);
+  }
+  if (part && repart) {
+    part_records(d_uv, m, d_rank, n_rank, items, items_b, pws, nullptr, false, s);
+    if (tm) tm->mark("partition");
+  }
+  r.start.assign(nb + 1, 0ull);
+  r.sorted = items_b;
+  r.spare = items;
+  if (m) {
+    uint16_t* digits = (uint16_t*)sc.get(nm.item_bins, m * 2);
+    unsigned long long* dstart = (unsigned long long*)sc.get(nm.bin_start, 513 * 8);
+    // the bin starts reach the host before the scatter runs: the buckets are cut meanwhile
+    r.sorted = group_by_bins(src, part, m, d_rank, n_rank, c.d_err, r.d_bins, nb, items, items_b,
+                             tmp, digits, dstart, s, c.h_bstart, c.bins_ev);
+    r.spare = r.sorted == items ? items_b : items;
+    if (tm) tm->mark("edge_pass");
+    HIP_CHECK(hipEventSynchronize(c.bins_ev));
+    r.start.assign(c.h_bstart, c.h_bstart + nb + 1);
+  }
+  if (want_counts) {
+    r.counts.resize(nb);
+    for (uint32_t i = 0; i < nb; ++i) r.counts[i] = r.start[i + 1] - r.start[i];
+  }
+  return r;
+}
+
 static void build_tree_dev(Ctx& c, const uint32_t* d_uv, uint64_t m, const uint32_t* d_rank,
                            uint32_t n_rank, uint32_t n_seq, uint32_t* d_parent, uint32_t* d_pst,
                            hipStream_t s, Timer* tm, const DegInfo* di = nullptr,
-                           bool allow_direct = true) {
+                           const Front* f = nullptr) {
   require_records(m, "tree build");
   if (n_seq == 0) return;
   launch_fill(d_parent, INV, n_seq, s);
@@ -882,140 +1210,41 @@ static void build_tree_dev(Ctx& c, const uint32_t* d_uv, uint64_t m, const uint3
   // pst from degrees (di) needs the run length of every hi: counted by k_kb_map.  Otherwise
   // pst_weight[lo] += 1 per record in the edge pass.
   bool pst_count = di != nullptr;
-  // Large inputs: rank gathers in partitioned order (launch_part_gather), via items_b/items.
-  bool part = use_part(m);
-  const uint32_t* src = d_uv;
-  // Hi bins (one scatter pass) when the degrees are at hand; else the two-pass radix sort.
+  // Hi bins (bin_records) when the degrees are at hand; else the two-pass radix sort.
   const bool use_bins = pst_count && m >= (1ull << 20) && n_seq > 256;
-  // The bins come from the chunk degree sums (seq order): they are summed and copied to the
-  // host BEFORE the second partition pass is enqueued, so the host cuts the bins while the GPU
-  // runs that pass instead of idling for the round trip.
-  const size_t nch = ((size_t)n_seq + 255) / 256;
-  if (use_bins) {
-    uint64_t* cds = (uint64_t*)c.scratch.get("chunk_deg", nch * 8);
-    launch_chunk_degsum(di->seq, di->deg, n_seq, cds, s, di->nsd);
-    if (c.h_chunks_n < nch) {
-      if (c.h_chunks) HIP_CHECK(hipHostFree(c.h_chunks));
-      c.h_chunks = nullptr;
-      c.h_chunks_n = 0;
-      HIP_CHECK(hipHostMalloc((void**)&c.h_chunks, nch * 8, hipHostMallocDefault));
-      c.h_chunks_n = nch;
-    }
-    HIP_CHECK(hipMemcpyAsync(c.h_chunks, cds, nch * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipEventRecord(c.bins_ev, s));
-  }
-  const bool direct = use_bins && allow_direct && knobs().bin_direct;
-  // the second pass's records packed to 6 bytes: only the direct edge pass reads them
-  const bool pre6 = part && direct && di && di->ids_checked && part_p6_ok(n_rank);
-  uint32_t* pws = part ? (uint32_t*)c.scratch.get("part_ws", PART_WS_WORDS * 4) : nullptr;
-  if (part) {
-    if (di && di->part_first_done) {  // pass 1 ran on c.side, beside the sequence sort
-      HIP_CHECK(hipStreamWaitEvent(s, c.part_ev[1], 0));
-      launch_part_second(items, m, d_rank, n_rank, items_b, pws, s, pre6, di->mid_slots,
-                         di->mid_caps, di->mid_p6, ff_groups());
-    } else {
-      launch_part_gather(d_uv, m, d_rank, n_rank, items, items_b, pws, s, di && di->yhist_ready,
-                         pre6);
-    }
-    src = (const uint32_t*)items_b;
-    if (tm) tm->mark("partition");
-  }
-  if (!direct && part && di && di->part_first_done && di->mid_caps) {
-    // The first pass wrote capacity regions (launch_front_fused / launch_part_first_caps) whose
-    // overflow word the direct branch reads with the bins' own; without direct binning (n_seq
-    // <= 256, or bin_direct 0) it is read here: an overflowed region lost records, so the
-    // partition is run again from the records.
-    HIP_CHECK(hipMemcpyAsync(c.h_pinned + 10, c.d_err + 3, 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (c.h_pinned[10]) {
-      DegInfo d2 = *di;
-      d2.part_first_done = false;
-      d2.mid_caps = false;
-      d2.mid_p6 = false;
-      d2.mid_slots = 0;
-      d2.yhist_ready = false;
-      build_tree_dev(c, d_uv, m, d_rank, n_rank, n_seq, d_parent, d_pst, s, tm, &d2, allow_direct);
-      return;
-    }
-  }
   const uint64_t* sorted;
   uint64_t* spare;
   Buckets given;
-  const uint32_t* dbins = nullptr;
-  uint32_t nbins = 0;
+  Binned b;
   SegPlan plan;
-  uint32_t* ovf = c.d_err + 1;  // a directly binned bin outgrew its capacity
-  if (direct) {
-    // Each bin gets a capacity region sized by its estimated records (+ slack); the edge pass
-    // fills them directly, and the buckets are cut on the estimate (any cuts are exact).
-    HIP_CHECK(hipEventSynchronize(c.bins_ev));
-    std::vector<uint64_t> hd(c.h_chunks, c.h_chunks + nch);
-    std::vector<double> est;
-    std::vector<uint32_t> bounds = make_bins(hd, n_seq, &est);
-    nbins = (uint32_t)bounds.size();
-    uint32_t* db = (uint32_t*)c.scratch.get("hi_bins", 512 * 4);
-    HIP_CHECK(hipMemcpyAsync(db, bounds.data(), nbins * 4, hipMemcpyHostToDevice, s));
-    dbins = db;
-    const double slack = 1.0 + knobs().bin_slack / 1000.0;
-    plan.cstart.assign(nbins, 0ull);
-    std::vector<unsigned long long> h(3 * 512, 0ull);  // start | cursor | capacity end
-    for (uint32_t i = 0; i + 1 < nbins; ++i) {
-      // a bin never holds more than m items (and the map keeps segment lengths in u32)
-      const uint64_t cap = std::min<uint64_t>((uint64_t)std::ceil(est[i] * slack) + 8192, m);
-      plan.cstart[i + 1] = plan.cstart[i] + cap;
-      h[i] = h[512 + i] = plan.cstart[i];
-      h[1024 + i] = plan.cstart[i + 1];
+  if (use_bins) {
+    b = bin_records(c, c.scratch, kTreeSlots, d_uv, m, d_rank, n_rank, di->seq, di->deg, di->nsd,
+                    n_seq, f ? *f : Front(), false, false, s, tm);
+    const uint32_t nbins = (uint32_t)b.bounds.size();
+    sorted = b.sorted;
+    spare = b.spare;
+    if (b.direct) {  // the buckets' .second are bin indices, cut on the capacities
+      plan.dev = {b.dseg, b.dseg + 512, b.dseg + 1024, 0u, 0u};
+      plan.cstart = b.start;
+      given.emplace_back(0u, 0ull);
+      for (uint32_t i : bucket_cuts(b.bounds, plan.cstart, m, n_seq))
+        given.emplace_back(b.bounds[i], i);
+      given.emplace_back(n_seq, (uint64_t)(nbins - 1));
+    } else {
+      given = buckets_from_bins(b.bounds, b.start, m, n_seq);
     }
-    unsigned long long* dseg = (unsigned long long*)c.scratch.get("bin_segs", h.size() * 8);
-    HIP_CHECK(hipMemcpyAsync(dseg, h.data(), h.size() * 8, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemsetAsync(ovf, 0, 4, s));
-    uint64_t* binned = (uint64_t*)c.scratch.get(
-        "e_binned", std::max<uint64_t>(plan.cstart[nbins - 1], 1) * 8);
-    launch_edge_bin(src, part, m, d_rank, n_rank, c.d_err, db, nbins, dseg + 512, dseg + 1024,
-                    binned, ovf, s, pre6 ? pws : nullptr);
-    if (tm) tm->mark("edge_pass");
-    // One readback before the kb loop is enqueued (the host then enqueues while the GPU runs
-    // the first buckets): a bin that outgrew its estimate holds a hole where its dropped runs
-    // were reserved, so the records are grouped again through the scatter.
-    // (with ovf the first partition pass's overflow word, c.d_err[3]: capacity regions)
-    HIP_CHECK(hipMemcpyAsync(c.h_pinned + 8, ovf, 12, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (c.h_pinned[8] || (di && di->mid_caps && c.h_pinned[10])) {
-      DegInfo d2 = *di;
-      d2.part_first_done = false;  // k_part's passes are run again from d_uv (unpacked)
-      d2.mid_caps = false;
-      d2.mid_p6 = false;
-      d2.mid_slots = 0;
-      d2.yhist_ready = false;      // the first partition consumed the y-digit counts
-      build_tree_dev(c, d_uv, m, d_rank, n_rank, n_seq, d_parent, d_pst, s, tm, &d2, false);
-      return;
-    }
-    plan.dev = {dseg, dseg + 512, dseg + 1024, 0u, 0u};
-    given.emplace_back(0u, 0ull);
-    for (uint32_t i : bucket_cuts(bounds, plan.cstart, m, n_seq)) given.emplace_back(bounds[i], i);
-    given.emplace_back(n_seq, (uint64_t)(nbins - 1));
-    sorted = binned;
-    spare = items;  // free: held k_part's mid records (src is items_b or d_uv)
-  } else if (use_bins) {
-    HIP_CHECK(hipEventSynchronize(c.bins_ev));
-    std::vector<uint64_t> hd(c.h_chunks, c.h_chunks + nch);
-    std::vector<uint32_t> bounds = make_bins(hd, n_seq);
-    nbins = (uint32_t)bounds.size();
-    uint32_t* db = (uint32_t*)c.scratch.get("hi_bins", 512 * 4);
-    HIP_CHECK(hipMemcpyAsync(db, bounds.data(), nbins * 4, hipMemcpyHostToDevice, s));
-    dbins = db;
-    uint16_t* digits = (uint16_t*)c.scratch.get("item_bins", m * 2);
-    unsigned long long* dstart = (unsigned long long*)c.scratch.get("bin_start", 513 * 8);
-    // the bin starts reach the host before the scatter runs: the buckets are cut meanwhile
-    uint64_t* out = group_by_bins(src, part, m, d_rank, n_rank, c.d_err, db, nbins, items, items_b,
-                                  tmp, digits, dstart, s, c.h_bstart, c.bins_ev);
-    if (tm) tm->mark("edge_pass");
-    HIP_CHECK(hipEventSynchronize(c.bins_ev));
-    std::vector<unsigned long long> hs(c.h_bstart, c.h_bstart + nbins + 1);
-    given = buckets_from_bins(bounds, hs, m, n_seq);
-    sorted = out;
-    spare = out == items ? items_b : items;
   } else {
+    // Large inputs: rank gathers in partitioned order (part_records), via items / items_b.
+    const uint32_t* src = d_uv;
+    const bool part = use_part(m);
+    if (part) {
+      uint32_t* pws = (uint32_t*)c.scratch.get("part_ws", PART_WS_WORDS * 4);
+      part_records(d_uv, m, d_rank, n_rank, items, items_b, pws, f, false, s);
+      if (f && f->part_done && f->mid_caps && mid_overflowed(c, s))
+        part_records(d_uv, m, d_rank, n_rank, items, items_b, pws, nullptr, false, s);
+      src = (const uint32_t*)items_b;
+      if (tm) tm->mark("partition");
+    }
     launch_edge_pass_tiles(src, m, d_rank, n_rank, pst_count ? nullptr : d_pst, items, c.d_err,
                            lo_bit, rsort_first_width(top + 1 - lo_bit), tmp, s, part);
     if (tm) tm->mark("edge_pass");
@@ -1030,7 +1259,8 @@ static void build_tree_dev(Ctx& c, const uint32_t* d_uv, uint64_t m, const uint3
   }
   unsigned long long* ws = (unsigned long long*)c.scratch.get("tree_ws", 64 * 2);
   tree_from_sorted(c, sorted, spare, m, n_seq, lo_bit, d_parent, jump, hcnt, stats, ws, s, tm,
-                   use_bins ? &given : nullptr, dbins, nbins, direct ? &plan : nullptr);
+                   use_bins ? &given : nullptr, b.d_bins, (uint32_t)b.bounds.size(),
+                   b.direct ? &plan : nullptr);
   if (tm) tm->mark("tree_insert");
   if (pst_count) {
     launch_pst_from_count(di->seq, n_seq, di->deg, di->selfc, di->mode, hcnt, d_pst, s, di->nsd);
@@ -1177,18 +1407,12 @@ struct Lockstep {
   }
 };
 
-// part_done (nullable): the first partition pass of the rank gathers was launched by the caller
-// into "ls_items" (with "part_ws" holding its cursors) and completes at this event.
+// f (nullable): what the caller's front half left (its first partition pass in "ls_items").
 // nsd (nullable): the global degrees in sequence order, read instead of d_deg[d_seq[r]].
-// mid_caps: the first pass wrote capacity regions of mid_slots records (launch_front_fused,
-// packed: mid_p6) whose overflow word is d_err[3]; an overflow sends this rank's partition
-// back to the unpacked records (as build_tree_dev does).
 static void ls_begin(Lockstep& L, const uint32_t* d_uv, uint64_t m, const uint32_t* d_rank,
                      uint32_t n_rank, const uint32_t* d_seq, uint32_t n_seq,
                      const uint32_t* d_deg, uint64_t* counts_out, uint32_t* nb_out,
-                     uint32_t* d_err, hipStream_t s, hipEvent_t part_done = nullptr,
-                     const uint32_t* nsd = nullptr, bool ids_checked = false,
-                     uint64_t mid_slots = 0, bool mid_caps = false, bool mid_p6 = false) {
+                     hipStream_t s, const Front* f = nullptr, const uint32_t* nsd = nullptr) {
   require_records(m, "lockstep");
   Scratch& sc = *L.scp;
   L.m = m;
@@ -1233,120 +1457,19 @@ static void ls_begin(Lockstep& L, const uint32_t* d_uv, uint64_t m, const uint32
     counts_out[0] = m;
     return;
   }
-  // hi bins from the global degrees (identical on every rank): the chunk sums go to pinned host
-  // memory, and the host cuts the bins while the second partition pass (which needs no bins)
-  // runs
-  Ctx& c = *L.ctx;
-  const size_t nch = ((size_t)n_seq + 255) / 256;
-  uint64_t* cds = (uint64_t*)sc.get("ls_chunk_deg", nch * 8);
-  launch_chunk_degsum(d_seq, d_deg, n_seq, cds, s, nsd);
-  if (c.h_chunks_n < nch) {
-    if (c.h_chunks) HIP_CHECK(hipHostFree(c.h_chunks));
-    c.h_chunks = nullptr;
-    c.h_chunks_n = 0;
-    HIP_CHECK(hipHostMalloc((void**)&c.h_chunks, nch * 8, hipHostMallocDefault));
-    c.h_chunks_n = nch;
-  }
-  HIP_CHECK(hipMemcpyAsync(c.h_chunks, cds, nch * 8, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipEventRecord(c.bins_ev, s));
-  // this shard's records -> items (hi, lo) grouped by bin
-  const uint64_t mm = std::max<uint64_t>(m, 1);
-  uint64_t* items = (uint64_t*)sc.get("ls_items", mm * 8);
-  uint64_t* items_b = (uint64_t*)sc.get("ls_items_b", mm * 8);
-  uint32_t* tmp = (uint32_t*)sc.get("ls_rsort_tmp", rsort_tmp_words(mm) * 4);
-  uint16_t* digits = (uint16_t*)sc.get("ls_item_bins", mm * 2);
-  const uint32_t* src = d_uv;
-  const bool part = use_part(m);
-  // the second pass's records packed to 6 bytes for the direct edge pass (ids_checked: an id
-  // >= n_rank fails the caller anyway)
-  const bool pre6 = part && knobs().bin_direct && m > 0 && n_seq > 0 && ids_checked &&
-                    part_p6_ok(n_rank);
-  uint32_t* pws = nullptr;
-  if (part) {
-    if (part_done) {  // pass 1 ran beside the degree all-reduce and the sequence
-      pws = (uint32_t*)sc.get("part_ws", PART_WS_WORDS * 4);
-      HIP_CHECK(hipStreamWaitEvent(s, part_done, 0));
-      launch_part_second(items, m, d_rank, n_rank, items_b, pws, s, pre6, mid_slots, mid_caps,
-                         mid_p6, ff_groups());
-    } else {
-      mid_caps = false;
-      pws = (uint32_t*)sc.get("ls_part_ws", PART_WS_WORDS * 4);
-      launch_part_gather(d_uv, m, d_rank, n_rank, items, items_b, pws, s, false, pre6);
-    }
-    src = (const uint32_t*)items_b;
-  }
-  HIP_CHECK(hipEventSynchronize(c.bins_ev));
-  std::vector<uint64_t> hd(c.h_chunks, c.h_chunks + nch);
-  std::vector<double> est;
-  L.bounds = make_bins(hd, n_seq, &est);
-  const uint32_t nb = (uint32_t)L.bounds.size();
-  L.bins = (uint32_t*)sc.get("ls_bins", 512 * 4);
-  HIP_CHECK(hipMemcpyAsync(L.bins, L.bounds.data(), nb * 4, hipMemcpyHostToDevice, s));
-  mid_caps = mid_caps && part && part_done;
-  bool part_ovf = false, part_checked = false;
-  // Direct binning, as the one-GPU path: this shard's share of each bin's estimate (the bins
-  // and estimates are global) sizes its capacity; a bin that outgrows it sends this rank
-  // through the scatter below (ranks may differ in that: only per-bin counts are exchanged).
-  if (knobs().bin_direct && m > 0) {
-    double W = 0;
-    for (double e : est) W += e;
-    const double share = W > 0 ? std::min(1.0, (double)m / W) : 1.0;
-    const double slack = 1.0 + knobs().bin_slack / 1000.0;
-    L.cstart.assign(nb, 0ull);
-    std::vector<unsigned long long> h(3 * 512, 0ull);
-    for (uint32_t i = 0; i + 1 < nb; ++i) {
-      const uint64_t cap = std::min<uint64_t>((uint64_t)std::ceil(est[i] * share * slack) + 8192, m);
-      L.cstart[i + 1] = L.cstart[i] + cap;
-      h[i] = h[512 + i] = L.cstart[i];
-      h[1024 + i] = L.cstart[i + 1];
-    }
-    L.dseg = (unsigned long long*)sc.get("ls_bin_segs", h.size() * 8);
-    HIP_CHECK(hipMemcpyAsync(L.dseg, h.data(), h.size() * 8, hipMemcpyHostToDevice, s));
-    uint32_t* ovf = (uint32_t*)sc.get("ls_ovf", 4);
-    HIP_CHECK(hipMemsetAsync(ovf, 0, 4, s));
-    uint64_t* binned = (uint64_t*)sc.get("ls_binned", std::max<uint64_t>(L.cstart[nb - 1], 1) * 8);
-    launch_edge_bin(src, part, m, d_rank, n_rank, d_err, L.bins, nb, L.dseg + 512, L.dseg + 1024,
-                    binned, ovf, s, pre6 ? pws : nullptr);
-    std::vector<unsigned long long> cur(nb);
-    HIP_CHECK(hipMemcpyAsync(cur.data(), L.dseg + 512, nb * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(L.h_pinned, ovf, 4, hipMemcpyDeviceToHost, s));
-    L.h_pinned[1] = 0;
-    if (mid_caps) HIP_CHECK(hipMemcpyAsync(L.h_pinned + 1, d_err + 3, 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    part_checked = true;
-    part_ovf = mid_caps && L.h_pinned[1] != 0;
-    if (L.h_pinned[0] == 0 && !part_ovf) {
-      L.direct = true;
-      L.sorted = binned;
-      for (uint32_t i = 0; i + 1 < nb; ++i) counts_out[i] = cur[i] - L.cstart[i];
-      counts_out[nb - 1] = 0;  // INVALID his are not stored (no bucket reads them)
-      *nb_out = nb;
-      return;
-    }
-  }
-  if (mid_caps && !part_checked) {  // (no direct binning: the regions' overflow word alone)
-    HIP_CHECK(hipMemcpyAsync(L.h_pinned + 1, d_err + 3, 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    part_ovf = L.h_pinned[1] != 0;
-  }
-  // A bin overflowed (the scatter path reads unpacked records), or a capacity region of the
-  // first pass did (its records are incomplete): partition again from the records.
-  if (pre6 || part_ovf) {
-    uint32_t* pws2 = (uint32_t*)sc.get("ls_part_ws", PART_WS_WORDS * 4);
-    launch_part_gather(d_uv, m, d_rank, n_rank, items, items_b, pws2, s, false, false);
-  }
-  unsigned long long* dstart = (unsigned long long*)sc.get("ls_bin_start", 513 * 8);
-  L.sorted = group_by_bins(src, part, m, d_rank, n_rank, d_err, L.bins, nb, items, items_b, tmp,
-                           digits, dstart, s);
-  if (m) {
-    L.local_start.resize(nb + 1);
-    HIP_CHECK(hipMemcpyAsync(L.local_start.data(), dstart, (nb + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-  } else {
-    L.local_start.assign(nb + 1, 0ull);
-  }
-  for (uint32_t i = 0; i < nb; ++i) counts_out[i] = L.local_start[i + 1] - L.local_start[i];
-  *nb_out = nb;
+  // This shard's records -> items grouped by the hi bins of the global degrees (identical on
+  // every rank), as the one-GPU path (bin_records).  Ranks may differ in taking the scatter
+  // after an overflow: only the per-bin counts are exchanged.
+  Binned b = bin_records(*L.ctx, sc, kLsSlots, d_uv, m, d_rank, n_rank, d_seq, d_deg, nsd, n_seq,
+                         f ? *f : Front(), true, true, s, nullptr);
+  L.bounds = std::move(b.bounds);
+  L.bins = b.d_bins;
+  L.sorted = b.sorted;
+  L.direct = b.direct;
+  L.dseg = b.dseg;
+  (b.direct ? L.cstart : L.local_start) = std::move(b.start);
+  std::copy(b.counts.begin(), b.counts.end(), counts_out);
+  *nb_out = (uint32_t)L.bounds.size();
 }
 
 // The split apply for rank `rank` of P (P > 1; after ls_begin).  Its own buffers are taken from
@@ -1711,53 +1834,10 @@ static uint32_t multi_tree(Ctx& c, Comm& comm, const uint32_t* d_uv, uint64_t m,
   uint32_t* selfc = (uint32_t*)c.scratch.get("mt_selfc", n * 4);
   uint32_t* deg = (uint32_t*)c.scratch.get("mt_deg", n * 4);
   uint32_t* rank = (uint32_t*)c.scratch.get("mt_rank", n * 4);
-  // The front half of this rank's shard, as graph2tree_dev's: from 2^25 records ONE read of the
-  // shard gives its degrees and the first partition pass of the rank gathers, packed into
-  // sampled capacity regions (launch_front_fused; part_overlap 4).  Else the first pass, which
-  // needs no ranks, runs on the side stream beside the degree pass, the degree collectives and
-  // the sequence.
-  const int ov = knobs().part_overlap;
-  const bool ffused = ov == 4 && m >= (1ull << 25) && use_part(m) && knobs().bin_direct &&
-                      knobs().degree != 1 && part_p6_ok(n_ids) && front_fused_ok(m, n_ids) &&
-                      degs_tmp_words(m, n_ids) > 1;
-  const uint64_t mid_slots = ffused ? front_fused_slots(m, n_ids, ff_groups()) : m;
-  const bool overlap = !ffused && ov != 0 && m > 0 && use_part(m);
-  hipEvent_t part_done = nullptr;
-  if (ffused) {
-    uint32_t* ovf_deg = c.d_err + 2;
-    HIP_CHECK(hipMemsetAsync(ovf_deg, 0, 8, s));  // both overflow words ([3]: the partition's)
-    uint32_t* tmp = (uint32_t*)c.scratch.get("degs_tmp", degs_tmp_words(m, n_ids) * 4);
-    uint32_t* pws = (uint32_t*)c.scratch.get("part_ws", PART_WS_WORDS * 4);
-    // (at least m u64: ls_begin takes the same buffer at that size and must not regrow it)
-    uint64_t* mid = (uint64_t*)c.scratch.get("ls_items", std::max<uint64_t>(m, mid_slots) * 8);
-    uint32_t* stats = (uint32_t*)c.scratch.get("stats", 16);
-    launch_front_fused(d_uv, m, n_ids, mode, deg_local, selfc, c.d_err, tmp, pws, mid, mid_slots,
-                       stats, ovf_deg, c.d_err + 3, s, nullptr, nullptr, ff_groups());
-    HIP_CHECK(hipEventRecord(c.part_ev[1], s));
-    part_done = c.part_ev[1];
-    // this shard's degrees are complete unless a region outgrew its capacity — an x bucket, or
-    // a y digit, whose ids the histogram counts from the packed records (a local decision: the
-    // exact pass has no collectives)
-    HIP_CHECK(hipMemcpyAsync(c.h_pinned + 4, ovf_deg, 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (tm) tm->mark("front_fused");
-    if (c.h_pinned[4] || c.h_pinned[5]) {
-      degree_dev(c, d_uv, m, n_ids, mode, deg_local, selfc, s);
-      if (tm) tm->mark("degree_exact");
-    }
-  }
-  if (overlap) HIP_CHECK(hipEventRecord(c.part_ev[0], s));  // in case degree_dev records none
-  const bool yh = ffused ? false
-                         : degree_dev(c, d_uv, m, n_ids, mode, deg_local, selfc, s, overlap,
-                                      overlap ? c.part_ev[0] : nullptr);
-  if (overlap) {
-    uint64_t* mid = (uint64_t*)c.scratch.get("ls_items", m * 8);
-    uint32_t* pws = (uint32_t*)c.scratch.get("part_ws", PART_WS_WORDS * 4);
-    HIP_CHECK(hipStreamWaitEvent(c.side, c.part_ev[0], 0));
-    launch_part_first(d_uv, m, n_ids, mid, pws, c.side, yh);
-    HIP_CHECK(hipEventRecord(c.part_ev[1], c.side));
-    part_done = c.part_ev[1];
-  }
+  // The front half of this rank's shard, the one graph2tree_dev runs (front_half).  A range error
+  // it saw is not thrown here: the device word stays set, and check_err_group below fails every
+  // rank with it after the degree collectives.
+  const Front f = front_half(c, "ls_items", d_uv, m, n_ids, mode, deg_local, selfc, false, s, tm);
   uint32_t n_seq = n_seq_given;
   const uint32_t* nsd = nullptr;  // sharded: the global degrees in sequence order
   if (!seq_given && comm.size() > 1 && knobs().ls_seq) {
@@ -1787,9 +1867,8 @@ static uint32_t multi_tree(Ctx& c, Comm& comm, const uint32_t* d_uv, uint64_t m,
   c.ls_live++;
   std::vector<uint64_t> counts(513, 0);
   uint32_t nb = 0;
-  ls_begin(L, d_uv, m, rank, n_ids, d_seq, n_seq, deg, counts.data(), &nb, c.d_err, s, part_done,
-           nsd, true, mid_slots, ffused, ffused);
-  if (part_done) HIP_CHECK(hipStreamWaitEvent(s, part_done, 0));  // also when no tree is built
+  ls_begin(L, d_uv, m, rank, n_ids, d_seq, n_seq, deg, counts.data(), &nb, s, &f, nsd);
+  if (f.part_done) HIP_CHECK(hipStreamWaitEvent(s, f.part_done, 0));  // also when no tree is built
   check_err_group(c, comm, s);
   uint64_t* dcounts = (uint64_t*)c.scratch.get("mt_counts", 513 * 8);
   HIP_CHECK(hipMemcpyAsync(dcounts, counts.data(), (size_t)nb * 8, hipMemcpyHostToDevice, s));
@@ -2080,137 +2159,25 @@ int sheep_graph2tree_dev(const uint32_t* d_uv, uint64_t m, uint32_t n_ids, int d
   uint32_t* deg = (uint32_t*)c.scratch.get("deg", (size_t)n_ids * 4);
   uint32_t* selfc = (uint32_t*)c.scratch.get("selfc", (size_t)n_ids * 4);
   uint32_t* rank = (uint32_t*)c.scratch.get("rank", (size_t)n_ids * 4);
-  // The first partition pass of the rank gathers needs no ranks, only the y-digit counts of
-  // the degree pass's first kernel: it runs on the side stream beside the rest of the degree
-  // pass and the sequence sort (SHEEP_PART_OVERLAP=0: in line, after them; =1: after the
-  // whole degree pass).
-  int ov = knobs().part_overlap;
-  uint32_t* stats = (uint32_t*)c.scratch.get("stats", 16);
-  // Fused (ov 3, and always past 2^31 records, where the endpoint offsets of the unfused
-  // degree pass end): the degree pass itself writes the records grouped by y bucket
-  // (launch_fh_front), so the first partition pass and its read are gone.  Not the default:
-  // it moves fewer bytes but in shorter runs, and measured no faster.
-  bool fused = false;
-  if ((ov == 3 || 2 * m >= (1ull << 32)) && use_part(m) && knobs().degree != 1 &&
-      fh_tmp_words(m, n_ids) > 1) {
-    require_records(m, "degree");  // its offsets count records, not endpoints
-    uint32_t* tmp = (uint32_t*)c.scratch.get("degb_tmp", fh_tmp_words(m, n_ids) * 4);
-    uint64_t* mid = (uint64_t*)c.scratch.get("e_items", m * 8);
-    uint32_t* pws = (uint32_t*)c.scratch.get("part_ws", PART_WS_WORDS * 4);
-    fused = launch_fh_front(d_uv, m, n_ids, degree_mode, deg, selfc, c.d_err, tmp, mid, pws,
-                            stats, s, [](void* t, const char* n) { ((Timer*)t)->mark(n); }, &tm);
-  }
-  // Fused sampled (ov 4): ONE read of the records for the degrees and the first partition pass
-  // (launch_front_fused; packed first-pass records in sampled capacity regions).
-  const bool ffused = !fused && ov == 4 && use_part(m) && knobs().bin_direct &&
-                      part_p6_ok(n_ids) && m >= (1ull << 25) && knobs().degree != 1 &&
-                      front_fused_ok(m, n_ids) && degs_tmp_words(m, n_ids) > 1;
-  if (ffused) fused = true;
-  if (ov == 4 && !ffused) ov = 2;  // (below 2^25 records, or ids it cannot take: beside)
-  const bool overlap = !fused && ov != 0 && m > 0 && use_part(m);
-  // Sampled capacities (from 2^25 records, the bucketed degree path, the first pass beside
-  // it): no counting read of the records — the degree scatter and the first partition pass
-  // write into capacity regions sized from a 1/256 sample (launch_degree_sampled).  A region
-  // that overflows sends the degrees (here, before the sequence reads them) or the partition
-  // (after the edge pass, with the hi bins' overflow) through the exact pass.
-  const bool sampled = overlap && knobs().bin_direct && part_p6_ok(n_ids) && ov == 2 &&
-                       m >= (1ull << 25) && 2 * m < (1ull << 32) && knobs().degree != 1 &&
-                       degs_tmp_words(m, n_ids) > 1;
-  // records the mid buffer holds (capacity regions: their largest possible sum)
-  const uint64_t mid_slots = ffused    ? front_fused_slots(m, n_ids, ff_groups())
-                             : sampled ? (fs_room(m, 1024) + 7) & ~7ull
-                                       : m;
-  uint32_t* ovf_deg = c.d_err + 2;
-  uint32_t* ovf_part = c.d_err + 3;
-  if (overlap) HIP_CHECK(hipEventRecord(c.part_ev[0], s));  // in case degree_dev records none
-  bool yh = false;
-  bool stats_host = false;  // the degree stats already read back (sequence_dev skips its readback)
-  if (ffused) {
-    HIP_CHECK(hipMemsetAsync(ovf_deg, 0, 8, s));  // both overflow words
-    uint32_t* tmp = (uint32_t*)c.scratch.get("degs_tmp", degs_tmp_words(m, n_ids) * 4);
-    uint32_t* pws = (uint32_t*)c.scratch.get("part_ws", PART_WS_WORDS * 4);
-    uint64_t* mid = (uint64_t*)c.scratch.get("e_items", std::max<uint64_t>(m, mid_slots) * 8);
-    launch_front_fused(d_uv, m, n_ids, degree_mode, deg, selfc, c.d_err, tmp, pws, mid, mid_slots,
-                       stats, ovf_deg, ovf_part, s,
-                       [](void* t, const char* n) { ((Timer*)t)->mark(n); }, &tm, ff_groups());
-    tm.mark("degree_hist");
-    HIP_CHECK(hipEventRecord(c.part_ev[1], s));
-    // One readback: the error word and both overflow words (d_err[0..3]) with the degree stats.
-    // The degrees are complete unless a region outgrew its capacity: an x bucket, or a y digit
-    // (the histogram counts y's ids from the packed records, which then lost the run's tail);
-    // an id out of range leaves the pass's record array short, which is reported here, before
-    // anything reads it (the check_err the sequence would otherwise need).
-    HIP_CHECK(hipMemcpyAsync(c.h_pinned + 4, c.d_err, 16, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(c.h_pinned, stats, 12, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (c.h_pinned[4] & ERR_RANGE) check_err(c, s);  // (throws -ERANGE, resetting the word)
-    stats_host = true;
-    if (c.h_pinned[6] || c.h_pinned[7]) {
-      degree_dev(c, d_uv, m, n_ids, degree_mode, deg, selfc, s, false, nullptr, stats);
-      tm.mark("degree_exact");
-      stats_host = false;  // (the exact pass rewrote them)
-    }
-  } else if (sampled) {
-    HIP_CHECK(hipMemsetAsync(ovf_deg, 0, 8, s));  // both overflow words
-    uint32_t* tmp = (uint32_t*)c.scratch.get("degs_tmp", degs_tmp_words(m, n_ids) * 4);
-    uint32_t* pws = (uint32_t*)c.scratch.get("part_ws", PART_WS_WORDS * 4);
-    launch_degree_sampled(d_uv, m, n_ids, degree_mode, deg, selfc, c.d_err, tmp, pws, mid_slots,
-                          stats, ovf_deg, s, c.part_ev[0]);
-  } else if (!fused) {
-    yh = degree_dev(c, d_uv, m, n_ids, degree_mode, deg, selfc, s, true,
-                    overlap && ov == 2 ? c.part_ev[0] : nullptr, stats);
-  }
-  if (!ffused) tm.mark(fused ? "degree_hist" : "degree");
-  if (fused && !ffused) HIP_CHECK(hipEventRecord(c.part_ev[1], s));
-  if (sampled) {
-    // (at least m u64: the tree build takes the same buffer at that size and must not regrow it)
-    uint64_t* mid = (uint64_t*)c.scratch.get("e_items", std::max<uint64_t>(m, mid_slots) * 8);
-    uint32_t* pws = (uint32_t*)c.scratch.get("part_ws", PART_WS_WORDS * 4);
-    HIP_CHECK(hipStreamWaitEvent(c.side, c.part_ev[0], 0));
-    const size_t sp = tm.span_begin("part_first", c.side);  // k_part<0>, live-timed for bench
-    launch_part_first_caps(d_uv, m, n_ids, mid, mid_slots, pws, ovf_part, c.side);
-    tm.span_end(sp, c.side);
-    HIP_CHECK(hipEventRecord(c.part_ev[1], c.side));
-    // the degrees are complete and valid unless a bucket outgrew its region (the stream syncs
-    // here once; sequence_dev would wait for the degree pass anyway)
-    HIP_CHECK(hipMemcpyAsync(c.h_pinned + 4, ovf_deg, 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (c.h_pinned[4]) {
-      degree_dev(c, d_uv, m, n_ids, degree_mode, deg, selfc, s, false, nullptr, stats);
-      tm.mark("degree_exact");
-    }
-  } else if (overlap) {
-    uint64_t* mid = (uint64_t*)c.scratch.get("e_items", m * 8);
-    uint32_t* pws = (uint32_t*)c.scratch.get("part_ws", PART_WS_WORDS * 4);
-    if (ov != 2) HIP_CHECK(hipEventRecord(c.part_ev[0], s));
-    HIP_CHECK(hipStreamWaitEvent(c.side, c.part_ev[0], 0));
-    const size_t sp = tm.span_begin("part_first", c.side);  // k_part<0>, live-timed for bench
-    launch_part_first(d_uv, m, n_ids, mid, pws, c.side, yh);
-    tm.span_end(sp, c.side);
-    HIP_CHECK(hipEventRecord(c.part_ev[1], c.side));
-  }
+  // The front half (front_half): the degrees and the first partition pass of the rank gathers.
+  const Front f = front_half(c, "e_items", d_uv, m, n_ids, degree_mode, deg, selfc, true, s, &tm);
+  if (f.err_range) check_err(c, s);  // (throws -ERANGE, resetting the word)
   uint32_t* nsd = (uint32_t*)c.scratch.get("nsd", (size_t)std::max<uint32_t>(n_ids, 1) * 4);
   uint32_t n_seq = sequence_dev(c, deg, n_ids, d_seq, rank, s, true, nsd, selfc, degree_mode,
-                                stats_host);
+                                f.stats_host);
   // an id out of range leaves the fused pass's record array short: report it before the
   // partition passes read the array (the stream is idle here: sequence_dev synchronised it;
-  // the sampled fused pass read its error word above, unless the exact degree pass ran since)
-  if (fused && !stats_host) check_err(c, s);
+  // the sampled fused pass read its error word itself, unless the exact degree pass ran since)
+  if (f.fused && !f.stats_host) check_err(c, s);
   tm.mark("sequence");
   DegInfo di;
   di.nsd = nsd;
-  di.part_first_done = overlap || fused;
-  di.mid_slots = mid_slots;
-  di.mid_caps = sampled || ffused;
-  di.mid_p6 = ffused;
-  di.ids_checked = true;
-  di.yhist_ready = yh;
   di.seq = d_seq;
   di.deg = deg;
   di.selfc = selfc;
   di.mode = degree_mode;
-  build_tree_dev(c, d_uv, m, rank, n_ids, n_seq, d_parent, d_pst, s, &tm, &di);
-  if (overlap) HIP_CHECK(hipStreamWaitEvent(s, c.part_ev[1], 0));  // also when no tree was built
+  build_tree_dev(c, d_uv, m, rank, n_ids, n_seq, d_parent, d_pst, s, &tm, &di, &f);
+  if (f.part_done) HIP_CHECK(hipStreamWaitEvent(s, f.part_done, 0));  // also when no tree was built
   check_err(c, s);
   tm.finish(c);
   if (n_seq_out) *n_seq_out = n_seq;
@@ -2524,8 +2491,7 @@ int sheep_ls_begin(const uint32_t* d_uv, uint64_t m, const uint32_t* d_rank, uin
   L->ctx = &c;
   L->scp = c.ls_live++ == 0 ? &c.scratch : &L->own;
   try {
-    ls_begin(*L, d_uv, m, d_rank, n_rank, d_seq, n_seq, d_deg, bin_counts_out, n_bins_out,
-             c.d_err, s);
+    ls_begin(*L, d_uv, m, d_rank, n_rank, d_seq, n_seq, d_deg, bin_counts_out, n_bins_out, s);
     check_err(c, s);
   } catch (...) {
     delete L;

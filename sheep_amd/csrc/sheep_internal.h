@@ -39,8 +39,9 @@ struct Knobs {
   int degree = 0;        // SHEEP_DEGREE: 0 auto (bucketed from 2^18 records), 1 atomic, 2 bucketed
   int edge_part = -1;    // SHEEP_EDGE_PART: partitioned rank gathers; -1 auto (m >= 2^22), 0, 1
   int part_overlap = 4;  // SHEEP_PART_OVERLAP: one read for the degrees and the first partition
-                         //   pass into sampled regions (4, graph2tree_dev from 2^25 records;
-                         //   else 2), the first pass beside the degree pass (2), after it (1),
+                         //   pass into sampled regions (4, from 2^25 records of the graph or of
+                         //   a rank's shard; else 2), the first pass beside the degree pass (2:
+                         //   both into sampled regions from 2^25 records), after it (1),
                          //   in line (0), fused into a counted degree scatter (3; taken anyway
                          //   from 2^31 records)
   int kb_buckets = 0;    // SHEEP_KB_BUCKETS: kb buckets cut at edge quantiles (0 = auto)
@@ -101,10 +102,6 @@ Ctx& ctx();  // this thread's context for the current device (sheep_gpu_init)
 // ---- launchers (sheep_kernels.hip); all enqueue on `s` -------------------------------------
 void launch_degree(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file_mode, uint32_t* deg,
                    uint32_t* selfc, uint32_t* err, hipStream_t s);
-// pst = nsdeg - run length of r in the hi-sorted items (start/end: n_seq scratch words each)
-void launch_pst_from_degree(const uint64_t* sorted, uint64_t m, const uint32_t* seq, uint32_t n_seq,
-                            const uint32_t* deg, const uint32_t* selfc, int file_mode,
-                            uint32_t* start, uint32_t* end, uint32_t* pst, hipStream_t s);
 // Bucketed LDS degree histogram for large m (same result as launch_degree); selfc nullable.
 size_t degb_tmp_words(uint64_t m, uint32_t n_ids, int* SH_out, uint32_t* NB_out);
 // yhist (nullable, 1024 words): also counts the y digits of launch_part_gather's first pass
@@ -134,7 +131,6 @@ size_t rsort_tmp_words(uint64_t n);
 int rsort_first_width(int bits);
 uint64_t* radix_sort_u64(const uint64_t* in, uint64_t* a, uint64_t* b, uint64_t n, int bit_lo,
                          int bit_hi, uint32_t* tmp, hipStream_t s, bool counted0 = false);
-void launch_pack_deg(const uint32_t* deg, uint32_t n, uint64_t* items, hipStream_t s);
 // (deg << 32 | id) of the ids with deg > 0 only, in id order; tmp: pack_nz_tmp_words(n) u32.
 size_t pack_nz_tmp_words(uint32_t n);
 void launch_pack_nonzero(const uint32_t* deg, uint32_t n, uint64_t* items, uint32_t* tmp,
@@ -148,19 +144,13 @@ void launch_unpack_seq(const uint64_t* items, uint32_t zeros, uint32_t n_seq, ui
 // to be sorted and unpacked from the position the returned device word (u64) holds.
 size_t seqc_tmp_words(uint32_t n);
 uint32_t seqc_threshold();
-// selfc (nullable): nsd = deg - w * selfc (w = 2 in FILE mode), as launch_nsd_selfloops.
+// selfc (nullable): nsd = deg - w * selfc (w = 2 in FILE mode).
 uint32_t* launch_seqc_place(const uint32_t* deg, uint32_t n, uint32_t* seq, uint32_t* rank,
                             uint32_t* nsd, uint64_t* big, uint32_t* tmp, hipStream_t s,
                             const uint32_t* selfc, int file_mode);
-// nsd[rank[v]] -= w * selfc[v] (w = 2 in FILE mode): the self-loop part of launch_unpack_seq's nsd.
-void launch_nsd_selfloops(const uint32_t* selfc, uint32_t n_ids, const uint32_t* rank,
-                          int file_mode, uint32_t* nsd, hipStream_t s);
 void launch_fill(uint32_t* p, uint32_t value, uint64_t n, hipStream_t s);
 void launch_rank_scatter(const uint32_t* seq, uint32_t n_seq, uint32_t* rank, uint32_t* err,
                          hipStream_t s);
-void launch_edge_pass(const uint32_t* uv, uint64_t m, const uint32_t* rank, uint32_t n_rank,
-                      uint32_t* pst /* nullable: no pst */, uint64_t* items, uint32_t* err,
-                      hipStream_t s);
 // edge pass + the first radix pass's tile histograms (sort bits from `shift`, DB wide)
 void launch_edge_pass_tiles(const uint32_t* uv, uint64_t m, const uint32_t* rank, uint32_t n_rank,
                             uint32_t* pst, uint64_t* items, uint32_t* err, int shift, int DB,
@@ -306,15 +296,10 @@ void launch_gb_sweep(uint32_t* uf, uint32_t* gbits, uint32_t B0lim, const uint32
                      hipStream_t s);
 // The giant's anchor for the next map, picked on the device among ranks [0, B0lim) (the
 // component holding most of an even sample; see sheep_kernels.hip), written to *anc_out (INV
-// when B0lim = 0); gbits (nullable): the bitmap is then rebased on it (launch_gb_rebase).
+// when B0lim = 0); gbits (nullable): the bitmap is then rebased on it (*gx_rd -> *gx_wr).
 void launch_kb_pick(const uint32_t* uf, uint32_t B0lim, const uint32_t* anc_prev, uint32_t* anc_out,
                     uint32_t* gbits, uint32_t n_seq, const uint32_t* gx_rd, uint32_t* gx_wr,
                     hipStream_t s);
-// Before a map (nothing else touching the union-find): keep the giant bitmap's reference
-// vertex (*gx_rd) if it is in the anchor's component, else move it to the anchor and clear
-// the bitmap (n_seq / 32 + 2 words); the result goes to *gx_wr.
-void launch_gb_rebase(uint32_t* gbits, uint32_t n_seq, const uint32_t* uf, uint32_t anchor,
-                      const uint32_t* gx_rd, uint32_t* gx_wr, hipStream_t s);
 // refresh: re-resolve the kept starts against the current union-find first (pipelined loop).
 // gbits / gx: the giant bitmap and the slot written by the latest rebase on this stream.
 void launch_kb_apply(bool nonempty, uint32_t B0, uint32_t B1, uint32_t anchor, uint32_t* uf,

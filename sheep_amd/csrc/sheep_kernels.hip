@@ -8,7 +8,8 @@
 //   k_rsort_*       stable LSD radix sort of packed u64 items, LDS-ranked and LDS-staged
 //                   8192-item tiles (degree sequence: sequence.h:55-61; edges by max(rank))
 //   k_scan_*        exclusive scan (radix offsets)
-//   k_edge_pass     rank translation, pst_weight (jtree.cpp:84-87), (lo,hi) tree edges
+//   k_edge_pass_tiles / k_edge_bin
+//                   rank translation, pst_weight (jtree.cpp:84-87), (lo,hi) tree edges
 //   k_tree_insert   lock-free elimination-tree insertion ("zipper"), replacing the
 //                   union-find loop jtree.cpp:73-83 + unionfind.h:46-102
 //   k_merge         associative tree union (jnode.cpp:174-201) with the same insertion
@@ -113,32 +114,8 @@ void launch_degree(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file_mode
 // that are not self-loops are either PREORDER (other endpoint earlier in seq: r is their hi)
 // or POSTORDER (other endpoint later, or not in seq): jtree.cpp:78-87.  So
 //     pst[r] = nsdeg[v] - |{records with hi == r}|,   nsdeg[v] = deg[v] - w * selfloops[v]
-// (w = 1 for LLAMA degrees, 2 for FILE degrees), and the second term is the length of r's run
-// in the hi-sorted edge list.
-__global__ void k_run_bounds(const uint64_t* __restrict__ items, uint64_t m,
-                             uint32_t* __restrict__ start, uint32_t* __restrict__ end) {
-  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride) {
-    uint32_t b = (uint32_t)(items[i] >> 32);
-    if (b == INV) continue;
-    uint32_t pb = i ? (uint32_t)(items[i - 1] >> 32) : INV;
-    uint32_t nb = i + 1 < m ? (uint32_t)(items[i + 1] >> 32) : INV;
-    if (b != pb) start[b] = (uint32_t)i;
-    if (b != nb) end[b] = (uint32_t)(i + 1);
-  }
-}
-
-__global__ void k_pst_from_degree(const uint32_t* __restrict__ seq, uint32_t n_seq,
-                                  const uint32_t* __restrict__ deg, const uint32_t* __restrict__ selfc,
-                                  uint32_t w, const uint32_t* __restrict__ start,
-                                  const uint32_t* __restrict__ end, uint32_t* __restrict__ pst) {
-  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_seq; r += gridDim.x * blockDim.x) {
-    uint32_t v = seq[r];
-    pst[r] = deg[v] - w * selfc[v] - (end[r] - start[r]);
-  }
-}
-
-// pst[r] = nsdeg[seq[r]] - cnt[r], cnt[r] = |{records with hi == r}| (counted by k_kb_map).
+// (w = 1 for LLAMA degrees, 2 for FILE degrees), and the second term cnt[r] is counted by
+// k_kb_map.
 // nsd (nullable): nsdeg already in rank order (k_unpack_seq), read instead of two gathers.
 __global__ void k_pst_from_count(const uint32_t* __restrict__ seq, uint32_t n_seq,
                                  const uint32_t* __restrict__ deg, const uint32_t* __restrict__ selfc,
@@ -160,17 +137,6 @@ void launch_pst_from_count(const uint32_t* seq, uint32_t n_seq, const uint32_t* 
   if (n_seq == 0) return;
   hipLaunchKernelGGL(k_pst_from_count, dim3(grid_for(n_seq)), dim3(BLOCK), 0, s, seq, n_seq, deg,
                      selfc, file_mode ? 2u : 1u, cnt, pst, nsd);
-}
-
-void launch_pst_from_degree(const uint64_t* sorted, uint64_t m, const uint32_t* seq, uint32_t n_seq,
-                            const uint32_t* deg, const uint32_t* selfc, int file_mode,
-                            uint32_t* start, uint32_t* end, uint32_t* pst, hipStream_t s) {
-  if (n_seq == 0) return;
-  (void)hipMemsetAsync(start, 0, (size_t)n_seq * 4, s);
-  (void)hipMemsetAsync(end, 0, (size_t)n_seq * 4, s);
-  if (m) hipLaunchKernelGGL(k_run_bounds, dim3(grid_for(m)), dim3(BLOCK), 0, s, sorted, m, start, end);
-  hipLaunchKernelGGL(k_pst_from_degree, dim3(grid_for(n_seq)), dim3(BLOCK), 0, s, seq, n_seq, deg,
-                     selfc, file_mode ? 2u : 1u, (const uint32_t*)start, (const uint32_t*)end, pst);
 }
 
 // stats[0] = max degree, stats[1] = number of zero-degree ids, stats[2] = number of ids of
@@ -1189,6 +1155,10 @@ k_degb_hist16(const uint16_t* __restrict__ ep, const uint32_t* __restrict__ offs
 // caller zeroed.  One workgroup per bucket left the step waiting on the buckets of the hub ids
 // and on the last round of buckets over the CUs.  Counting as k_degb_hist16 (u16 halves of
 // 32768 LDS words, segments of at most 65535 entries, u32 totals in registers).
+// REQUIRES the fused front pass's cursor layout: xf / yf are k_front_fused's region cursors,
+// spread over memory (cursor q at u64 index fs_cix(q), sheep_internal.h), while xs / ys are
+// plain arrays of region starts.  Cursors laid out contiguously (the sampled degree pass's) would
+// be read at the wrong words: only launch_front_fused may launch these.
 // Slices of bucket t (thread t of a 1024-thread block, t < NB) and the first slice's block
 // index (an exclusive scan over the buckets; wsum: DEGB_THREADS / 64 words of LDS).
 __device__ __forceinline__ void hist16s_slices(const unsigned long long* __restrict__ xs,
@@ -2179,14 +2149,8 @@ uint64_t* radix_sort_u64(const uint64_t* in, uint64_t* a, uint64_t* b, uint64_t 
 
 // Degree sequence helpers: items = (deg << 32 | id); after the sort, seq = ids past the
 // zero-degree prefix and rank[seq[i]] = i (jtree.h:165-168) in the same pass.
-__global__ void k_pack_deg(const uint32_t* __restrict__ deg, uint32_t n, uint64_t* __restrict__ items) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    items[i] = ((uint64_t)deg[i] << 32) | i;
-}
-
 // nsd (nullable): nsd[i] = degree of seq[i] in rank order (the sorted item's key), less
-// w * selfc[seq[i]] when selfc is given; otherwise k_nsd_selfloops takes the self-loop records
-// off afterwards (a sparse pass instead of a gather per rank).
+// w * selfc[seq[i]] when selfc is given.
 __global__ void k_unpack_seq(const uint64_t* __restrict__ items, uint32_t zeros, uint32_t n_seq,
                              uint32_t* __restrict__ seq, uint32_t* __restrict__ rank,
                              uint32_t* __restrict__ nsd, const uint32_t* __restrict__ selfc,
@@ -2197,17 +2161,6 @@ __global__ void k_unpack_seq(const uint64_t* __restrict__ items, uint32_t zeros,
     seq[base + i] = v;
     if (rank) rank[v] = base + i;
     if (nsd) nsd[base + i] = (uint32_t)(it >> 32) - (selfc ? w * selfc[v] : 0u);
-  }
-}
-
-// nsd[rank[v]] -= w * selfc[v] for the ids with self-loop records (they have deg > 0, so a
-// rank): a coalesced read of selfc, random accesses only where it is non-zero.
-__global__ void k_nsd_selfloops(const uint32_t* __restrict__ selfc, uint32_t n_ids,
-                                const uint32_t* __restrict__ rank, uint32_t w,
-                                uint32_t* __restrict__ nsd) {
-  for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < n_ids; v += gridDim.x * blockDim.x) {
-    const uint32_t c = selfc[v];
-    if (c) nsd[rank[v]] -= w * c;
   }
 }
 
@@ -2270,23 +2223,12 @@ void launch_pack_nonzero(const uint32_t* deg, uint32_t n, uint64_t* items, uint3
   hipLaunchKernelGGL(k_pack_nz, dim3(nb), dim3(1024), 0, s, deg, n, (const uint32_t*)bofs, items);
 }
 
-void launch_pack_deg(const uint32_t* deg, uint32_t n, uint64_t* items, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_pack_deg, dim3(grid_for(n)), dim3(BLOCK), 0, s, deg, n, items);
-}
-
 void launch_unpack_seq(const uint64_t* items, uint32_t zeros, uint32_t n_seq, uint32_t* seq,
                        uint32_t* rank, hipStream_t s, uint32_t* nsd, const uint32_t* selfc,
                        int file_mode, uint32_t base) {
   if (n_seq)
     hipLaunchKernelGGL(k_unpack_seq, dim3(grid_for(n_seq)), dim3(BLOCK), 0, s, items, zeros, n_seq,
                        seq, rank, nsd, selfc, file_mode ? 2u : 1u, base);
-}
-
-void launch_nsd_selfloops(const uint32_t* selfc, uint32_t n_ids, const uint32_t* rank,
-                          int file_mode, uint32_t* nsd, hipStream_t s) {
-  if (n_ids)
-    hipLaunchKernelGGL(k_nsd_selfloops, dim3(grid_for(n_ids)), dim3(BLOCK), 0, s, selfc, n_ids, rank,
-                       file_mode ? 2u : 1u, nsd);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2435,38 +2377,7 @@ void launch_rank_scatter(const uint32_t* seq, uint32_t n_seq, uint32_t* rank, ui
 //   lo, hi both valid  -> tree edge (lo, hi)         (the PREORDER edge seen from hi)
 // Ids >= n_rank are outside the reference's index vector: if the other endpoint is in seq the
 // reference's index.at() throws (jtree.cpp:75) -> ERR_RANGE; otherwise neither endpoint is
-// ever visited and the record is ignored.
-// ---------------------------------------------------------------------------------------
-__global__ void k_edge_pass(const uint2* __restrict__ uv, uint64_t m,
-                            const uint32_t* __restrict__ rank, uint32_t n_rank,
-                            uint32_t* __restrict__ pst, uint64_t* __restrict__ items, uint32_t* err) {
-  uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride) {
-    uint2 e = uv[i];
-    uint32_t hi = INV, lo = INV;
-    if (e.x != e.y) {
-      bool ox = e.x >= n_rank, oy = e.y >= n_rank;
-      uint32_t rx = ox ? INV : rank[e.x];
-      uint32_t ry = oy ? INV : rank[e.y];
-      if ((ox && ry != INV) || (oy && rx != INV)) {
-        atomicOr(err, ERR_RANGE);
-      } else {
-        lo = min(rx, ry);
-        hi = max(rx, ry);
-        if (lo != INV && pst) atomicAdd(&pst[lo], 1u);
-      }
-    }
-    items[i] = ((uint64_t)hi << 32) | lo;
-  }
-}
-
-void launch_edge_pass(const uint32_t* uv, uint64_t m, const uint32_t* rank, uint32_t n_rank,
-                      uint32_t* pst, uint64_t* items, uint32_t* err, hipStream_t s) {
-  if (m == 0) return;
-  hipLaunchKernelGGL(k_edge_pass, dim3(grid_for(m)), dim3(BLOCK), 0, s, (const uint2*)uv, m, rank,
-                     n_rank, pst, items, err);
-}
-
+// ever visited and the record is ignored.  (k_edge_pass_tiles and k_edge_bin below.)
 // ---------------------------------------------------------------------------------------
 // Hi bins: one radix-style pass instead of the two 9-bit passes.  The kb loop needs the
 // records grouped by hi only down to 256-rank groups, and only where they are dense; the bins
@@ -2506,7 +2417,7 @@ void launch_chunk_degsum(const uint32_t* seq, const uint32_t* deg, uint32_t n_se
 // The edge pass fused with the first radix pass's tile histograms (digit = bits
 // [shift, shift + DB) of hi): one block per RS_TILE records, wave-striped like
 // k_rsort_count; each thread loads its 8 records and issues their rank gathers before using
-// any (keep many gathers in flight).  pst (nullable) as in k_edge_pass.
+// any (keep many gathers in flight).  pst (nullable): pst_weight[lo] += 1 per record (above).
 // PRE: the records are k_part's output (x, ry): rank[y] was gathered already (or is one of the
 // sentinels RY_SELF / RY_OUT), only rank[x] is gathered here.
 // TM: the tile histograms are written tile-major (bin_sort_u64's k_tm_* passes).
@@ -3733,14 +3644,14 @@ __device__ __forceinline__ void uf_union(uint32_t* uf, uint32_t u, uint32_t v, u
 //   cnt[b] += 1 (nullable: the run length of b that pst needs).
 // Giant membership without the union-find: gbits (nullable) holds one bit per rank, set only
 // for ranks known to lie in the component of the reference vertex X = *gx; the rebase before
-// this launch (k_gb_rebase) made X a member of the anchor's component, so a set bit means
+// this launch (k_kb_pick) made X a member of the anchor's component, so a set bit means
 // g = G with no find at all.  Only the other records (non-giant components, and giant members
 // whose bit is not set yet) run the find, and those finds are batched: every lane first loads
 // its KM_R records and their bitmap words, then walks all of its misses' chains together (the
 // loads of different records interleave), and a miss that reaches the giant sets its bit for
 // the records that follow.  Bits are set by this map, by k_kb_spine (the bucket's marked ranks)
 // and by k_kb_label (the bucket's ranks that ended in X's component); they are only ever
-// cleared by k_gb_rebase when X moves to another component (before the giant has formed).
+// cleared by k_kb_pick when X moves to another component (before the giant has formed).
 // A block takes chunks of KM_CHUNK records; marks and counts of ranks within KM_WIN of the
 // chunk's first group go to LDS (bitmap + packed 16-bit counts) and reach global memory once
 // per word per chunk — a hub's records span many waves, and same-word atomics from every
@@ -4155,16 +4066,6 @@ void launch_gb_sweep(uint32_t* uf, uint32_t* gbits, uint32_t B0lim, const uint32
                      uf, gbits, B0lim, gx);
 }
 
-__global__ void k_gb_rebase(uint32_t* gbits, uint32_t nwords, const uint32_t* uf, uint32_t anchor,
-                            const uint32_t* __restrict__ gx_rd, uint32_t* gx_wr) {
-  const uint32_t X = *gx_rd;
-  bool keep = anchor == INV || (X != INV && uf_find_ro(uf, X) == uf_find_ro(uf, anchor));
-  if (blockIdx.x == 0 && threadIdx.x == 0) *gx_wr = anchor == INV ? INV : (keep ? X : anchor);
-  if (!keep)
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += gridDim.x * blockDim.x)
-      gbits[i] = 0;
-}
-
 // The giant's anchor, picked on the device before the map of a bucket, with nothing else
 // running on the union-find.  The host's choice, rank B0lim - 1 (the highest degree among the
 // applied ranks [0, B0lim)), can sit outside the giant: its bucket then sees no giant records
@@ -4178,8 +4079,9 @@ __global__ void k_gb_rebase(uint32_t* gbits, uint32_t nwords, const uint32_t* uf
 //   else a sampled rank of the best component, if it holds >= 3 samples;
 //   else B0lim - 1 (no dominant component yet: the host's choice).
 // Any applied rank is exact as an anchor (see launch_kb_map); the choice only shapes the work.
-// B0lim = 0: no anchor (INV).  gbits (nullable): the bitmap is then rebased on the anchor as
-// k_gb_rebase does.
+// B0lim = 0: no anchor (INV).  gbits (nullable): the bitmap is then rebased on the anchor:
+// its reference vertex (*gx_rd) stays if it is in the anchor's component, else it moves to the
+// anchor and the bitmap (n_seq / 32 + 2 words) is cleared; the result goes to *gx_wr.
 static constexpr int KP = BLOCK;  // samples (one per thread of a block)
 __global__ void __launch_bounds__(BLOCK)
 k_kb_pick(const uint32_t* uf, uint32_t B0lim, const uint32_t* __restrict__ anc_prev,
@@ -4304,7 +4206,9 @@ __global__ void k_kb_spine(const uint32_t* __restrict__ bitmap, uint32_t B0, uin
 // of a without this edge (zip_step would stop it at its first step; here it costs two bitmap
 // reads in a flat stream instead of a lane of the zipper's queue).  A mark this launch has not
 // set yet only keeps a pair.
-// pj (nullable; the one-GPU apply): the zipper's first step for a pair whose start is a
+// pj (nullable; every launch_kb_apply — the one-GPU loop's and the lockstep loop's replicated,
+// non-split apply — unless the option kb_rlink is 0; null in the split apply's
+// launch_kb_refresh): the zipper's first step for a pair whose start is a
 // pre-bucket root g' (every pair that reaches no giant): g' had no parent before this bucket
 // (so no hint either), and zip_step's first move from it is exactly CAS(parent[g'], INVALID,
 // b).  Done here, in this flat pass with the pair already in registers, instead of through the
@@ -4543,7 +4447,7 @@ void launch_kb_bounds(const uint64_t* items, uint64_t n, uint32_t K_e, uint32_t 
 // component at B0.  (The pipelined loop maps bucket k+1 while bucket k is applied, so it
 // anchors at the last rank of bucket k-1.)  INV: no giant (first buckets).
 // gbits / gx (nullable): the giant bitmap and the slot of its reference vertex that
-// launch_gb_rebase wrote before this map.
+// launch_kb_pick wrote before this map.
 void launch_kb_map(const uint64_t* items, uint64_t e_begin, uint64_t e_end, uint32_t B0,
                    uint32_t anchor, uint32_t* uf, const uint32_t* label, uint64_t* kept,
                    uint64_t kept_cap, uint32_t* bitmap, uint32_t* counters, int gshift, uint32_t* cnt, bool stats,
@@ -4584,13 +4488,6 @@ void launch_kb_pick(const uint32_t* uf, uint32_t B0lim, const uint32_t* anc_prev
   const unsigned grid = gbits ? std::min<uint32_t>((nwords + BLOCK - 1) / BLOCK, 1024) : 1u;
   hipLaunchKernelGGL(k_kb_pick, dim3(grid), dim3(BLOCK), 0, s, uf, B0lim, anc_prev, anc_out, gbits,
                      nwords, gx_rd, gx_wr);
-}
-
-void launch_gb_rebase(uint32_t* gbits, uint32_t n_seq, const uint32_t* uf, uint32_t anchor,
-                      const uint32_t* gx_rd, uint32_t* gx_wr, hipStream_t s) {
-  const uint32_t nwords = n_seq / 32 + 2;
-  hipLaunchKernelGGL(k_gb_rebase, dim3(std::min<uint32_t>((nwords + BLOCK - 1) / BLOCK, 1024)),
-                     dim3(BLOCK), 0, s, gbits, nwords, uf, anchor, gx_rd, gx_wr);
 }
 
 static bool kb_refresh_links() { return knobs().kb_rlink != 0; }

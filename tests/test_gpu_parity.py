@@ -221,13 +221,12 @@ def test_graph2tree_dev_sampled_capacities_overflow(oracle, gpu, options, ov):
     import torch
     from sheep_amd import capi, device
 
+    from overflow_inputs import N_IDS, SharedReference, to_device, xy_overflow_records
+
     options(part_overlap=ov)
-    m, n_ids = 1 << 25, 1 << 20
-    rng = np.random.default_rng(3)
-    uv = rng.integers(0, n_ids, size=(m, 2), dtype=np.uint32)
-    uv[::256] = (0, 1)
-    uv_d = torch.from_numpy(uv.view(np.int32)).cuda().view(torch.uint32)
-    s_d, p_d, w_d, n = device.graph2tree(uv_d, n_ids)
+    oracle = SharedReference(oracle, "xy_overflow")
+    uv = xy_overflow_records()
+    s_d, p_d, w_d, n = device.graph2tree(to_device(uv), N_IDS)
     torch.cuda.synchronize()
     assert "degree_exact" in dict(capi.last_timings())
     seq = oracle.degree_sequence(uv)
@@ -248,15 +247,12 @@ def test_graph2tree_dev_fused_y_overflow_only(oracle, gpu, options, ff):
     import torch
     from sheep_amd import capi, device
 
+    from overflow_inputs import N_IDS, SharedReference, to_device, y_overflow_records
+
     options(ff_groups=ff)
-    m, n_ids = 1 << 25, 1 << 20
-    rng = np.random.default_rng(21)
-    uv = rng.integers(0, n_ids, size=(m, 2), dtype=np.uint32)
-    keep = np.zeros(m, bool)
-    keep[::256] = True
-    uv[~keep, 1] = rng.integers(5 << 10, 6 << 10, size=int((~keep).sum()), dtype=np.uint32)
-    uv_d = torch.from_numpy(uv.view(np.int32)).cuda().view(torch.uint32)
-    s_d, p_d, w_d, n = device.graph2tree(uv_d, n_ids)
+    oracle = SharedReference(oracle, "y_overflow")
+    uv = y_overflow_records()
+    s_d, p_d, w_d, n = device.graph2tree(to_device(uv), N_IDS)
     torch.cuda.synchronize()
     assert "degree_exact" in dict(capi.last_timings())
     seq = oracle.degree_sequence(uv)

@@ -157,3 +157,57 @@ def test_multi_local_one_rank_overflows(oracle, gpu):
     b = torch.from_numpy(np.ascontiguousarray(uv[order[cut:]]).view(np.int32)).cuda()
     out = device.graph2tree_multi_local([a.view(torch.uint32), b.view(torch.uint32)], 1 << 19)
     check(oracle, uv, 0, *out)
+
+
+def _one_rank_group(oracle, name, uv, n_ids):
+    """graph2tree_multi over a one-rank RCCL group (the code every rank of the 8-GPU run
+    executes), bit-exact; returns the call's phase timings."""
+    import torch
+    from overflow_inputs import SharedReference, to_device
+    from sheep_amd import capi, device
+
+    device.comm_init(device.comm_unique_id(), 1, 0)
+    try:
+        out = device.graph2tree_multi(to_device(uv), n_ids)
+        torch.cuda.synchronize()
+        t = dict(capi.last_timings())
+    finally:
+        device.comm_free()
+    check(SharedReference(oracle, name), uv, 0, *out)
+    return t
+
+
+@pytest.mark.parametrize("ff", [1, 8])
+def test_rccl_one_rank_fused_y_overflow_only(oracle, gpu, options, ff):
+    """The multi-rank driver's front half is the one-GPU driver's (front_half): only the y regions
+    of the fused pass overflow (test_graph2tree_dev_fused_y_overflow_only's input), and the exact
+    degree pass must run on the y flag alone, with either tile-group count."""
+    from overflow_inputs import N_IDS, y_overflow_records
+
+    options(ff_groups=ff)
+    t = _one_rank_group(oracle, "y_overflow", y_overflow_records(), N_IDS)
+    assert "degree_exact" in t
+
+
+@pytest.mark.parametrize("ov", [4, 2])
+def test_rccl_one_rank_sampled_capacities_overflow(oracle, gpu, options, ov):
+    """The same entry where x buckets and y digits overflow
+    (test_graph2tree_dev_sampled_capacities_overflow's input), fused (4) or sampled beside (2):
+    the exact degree pass and the regrouping's fallback to the unpacked records."""
+    from overflow_inputs import N_IDS, xy_overflow_records
+
+    options(part_overlap=ov)
+    t = _one_rank_group(oracle, "xy_overflow", xy_overflow_records(), N_IDS)
+    assert "degree_exact" in t
+
+
+def test_multi_local_one_rank_front_overflows(oracle, gpu):
+    """Two ranks of 2^25 records each, one whose fused pass overflows in y (the y-overflow-only
+    input) and one with uniform records: only rank 0 takes the exact degree pass and the
+    fallback of its partition, while both stay in the same collectives."""
+    from overflow_inputs import N_IDS, SharedReference, to_device, uniform_records, y_overflow_records
+    from sheep_amd import device
+
+    a, b = y_overflow_records(), uniform_records(22)
+    out = device.graph2tree_multi_local([to_device(a), to_device(b)], N_IDS)
+    check(SharedReference(oracle, "y_overflow+uniform"), np.concatenate([a, b]), 0, *out)
