@@ -271,44 +271,76 @@ void launch_edge_bin(const uint32_t* uv, bool pre, uint64_t m, const uint32_t* r
                      uint32_t n_rank, uint32_t* err, const uint32_t* bins, uint32_t nb,
                      unsigned long long* cursor, const unsigned long long* cap_end, uint64_t* out,
                      uint32_t* ovf, hipStream_t s, const uint32_t* part_ws = nullptr);
+// The device state of one kb loop (the bucket-synchronous tree loop of tree_from_sorted and of
+// the lockstep sessions; kb_state_init in sheep_capi.cpp allocates and initialises it).  Which
+// set or slot a bucket uses is written once, in the accessors.
+struct KbState {
+  uint32_t n_seq = 0;
+  size_t bm_words = 0;   // words of one mark bitmap and of the giant bitmap (n_seq / 32 + 2)
+  size_t spq_words = 0;  // words of one spine queue (n_seq / 32 + 64)
+  // Parent and hint interleaved (pj[2v], pj[2v + 1]; launch_pj_init): a zipper step loads one
+  // line.  The parents are copied out after the loop (launch_pj_parents).
+  uint32_t* pj = nullptr;
+  uint32_t* parent() const { return pj; }
+  uint32_t* jump() const { return pj + 1; }
+  uint32_t* uf = nullptr;      // union-find over the ranks (iota)
+  uint32_t* label = nullptr;   // a root's component's elimination-tree root (iota)
+  uint32_t* linked = nullptr;  // the pre-bucket roots a zipper linked, for the bucket's union
+  // 16 words per set, zero before the first bucket: [1] n_linked, [2] n_spine, [3] n_kept (each
+  // bucket's label kernel resets its set)
+  uint32_t* counters = nullptr;
+  uint32_t* bitmap = nullptr;  // the marks (the giant's records into a bucket): bm_words per set
+  uint32_t* spq = nullptr;     // the spine queues: spq_words per set
+  uint32_t* gbits = nullptr;  // giant bitmap (k_kb_map): bit v = v is in its reference vertex's
+  uint32_t* gx = nullptr;     //   component; that vertex, in two slots (INV: none yet)
+  // Giant summary the maps test first (bit q: ranks [64q, 64q + 64) all set in gbits; n_seq /
+  // 2048 + 1 words), rewritten by each rebase.  Nullable: it pays on large inputs only.
+  uint32_t* gsum = nullptr;
+  // The giant's anchor of each map, picked on the device (launch_kb_rebase), in two slots; the
+  // kernels take the slot's rank unless the host's anchor rank is INV (no giant yet).
+  uint32_t* anc = nullptr;
+  unsigned long long* st = nullptr;  // 16 stats words (diagnostics; the zipper's from st + 8)
+  uint32_t* hcnt = nullptr;          // nullable: the maps add each hi's run length (for pst)
+  // Counters, marks and spine queues alternate between two sets by bucket parity, so that map
+  // k + 1 may run beside apply k (false: one set, a loop that never overlaps them).
+  bool two_sets = true;
+  size_t set_of(size_t k) const { return two_sets ? (k & 1) : 0; }
+  uint32_t* cnt_of(size_t k) const { return counters + set_of(k) * 16; }
+  uint32_t* bm_of(size_t k) const { return bitmap + set_of(k) * bm_words; }
+  uint32_t* spq_of(size_t k) const { return spq + set_of(k) * spq_words; }
+  // Map j reads its anchor and the bitmap's reference vertex from slot j & 1.  The rebase for
+  // map j (launch_kb_rebase) reads slot (j - 1) & 1, what map j - 1 used, and writes slot j & 1,
+  // at a point where nothing else touches the union-find (map j - 1 and apply j - 1 complete);
+  // an apply passes the j of the latest rebase on its stream.
+  uint32_t* gx_of(size_t j) const { return gx + (j & 1); }
+  uint32_t* anc_of(size_t j) const { return anc + (j & 1); }
+};
 // One kb bucket in two halves (sheep_kernels.hip): the map (records -> kept pairs + giant marks
-// + hi counts) and the apply (spine, zipper, union-find fold, labels).  counters: this
-// bucket parity's 4 words; anchor: see launch_kb_map.
+// + hi counts) and the apply (spine, zipper, union-find fold, labels).
+// anchor: a rank whose component is taken as the giant (INV: none; sheep_kernels.hip).  segs
+// (nullable): the records were binned directly, e_begin / e_end bound its bins' capacity.
 // kept_cap: the u64 slots kept holds (a reservation past it raises the fault word, -EIO).
-void launch_kb_map(const uint64_t* items, uint64_t e_begin, uint64_t e_end, uint32_t B0,
-                   uint32_t anchor, uint32_t* uf, const uint32_t* label, uint64_t* kept,
-                   uint64_t kept_cap, uint32_t* bitmap, uint32_t* counters, int gshift,
-                   uint32_t* cnt /* nullable: hi run lengths */, bool stats,
-                   unsigned long long* st, const uint32_t* bins /* nullable: hi bins */,
-                   uint32_t nb, uint32_t* gbits /* nullable: giant bitmap */,
-                   const uint32_t* gx /* its reference-vertex slot (nullable: no bitmap) */,
-                   int defer /* 1: misses kept as (b, a) for launch_kb_apply's refresh;
-                                2: as (b, root of a) (split lockstep); 0: as (b, label) */,
-                   hipStream_t s, const KbSegs* segs = nullptr,
-                   const uint32_t* anc = nullptr /* device-picked anchor (launch_kb_pick) */,
-                   const uint32_t* gsum = nullptr /* giant summary (launch_gb_sum) */);
-// Giant summary for the next map (nothing writing gbits): bit q = ranks [64q, 64q + 64) all set
-// in gbits; (n_seq / 2048 + 1) words.
-void launch_gb_sum(const uint32_t* gbits, uint32_t n_seq, uint32_t* gsum, hipStream_t s);
+// gshift, bins / nb (nullable): how the items are grouped by hi.  defer: 1: misses kept as
+// (b, a) for launch_kb_apply's refresh; 2: as (b, root of a) (split lockstep); 0: as (b, label).
+void launch_kb_map(const KbState& S, size_t k, const uint64_t* items, uint64_t e_begin,
+                   uint64_t e_end, const KbSegs* segs, uint32_t B0, uint32_t anchor,
+                   uint64_t* kept, uint64_t kept_cap, int gshift, const uint32_t* bins,
+                   uint32_t nb, int defer, bool stats, hipStream_t s);
+// Before map j (j >= 1), with nothing else running on the union-find: the giant's anchor for
+// map j, picked on the device among ranks [0, B0lim) (the component holding most of an even
+// sample; INV when B0lim = 0), the giant bitmap rebased on it, and the giant summary (if any)
+// of the rebased bitmap.
+void launch_kb_rebase(const KbState& S, size_t j, uint32_t B0lim, hipStream_t s);
 // Giant sweep (sheep_kernels.hip k_gb_sweep): the giant bits of every rank v < B0lim in the
-// component of *gx, with nothing that may move *gx running beside it.
-void launch_gb_sweep(uint32_t* uf, uint32_t* gbits, uint32_t B0lim, const uint32_t* gx,
+// component of the bitmap's reference vertex (slot gx_slot, as launch_kb_apply), with nothing
+// that may move that vertex running beside it.
+void launch_gb_sweep(const KbState& S, uint32_t B0lim, size_t gx_slot, hipStream_t s);
+// Apply of bucket k = ranks [B0, B1) over its kept pairs.  refresh: re-resolve the kept starts
+// against the current union-find first (the map ran beside an earlier apply).  gx_slot: the j
+// of the latest rebase on this stream.  The union keeps the root of map k + 1's anchor on top.
+void launch_kb_apply(const KbState& S, size_t k, uint32_t B0, uint32_t B1, uint32_t anchor,
+                     bool nonempty, uint64_t* kept, bool refresh, bool stats, size_t gx_slot,
                      hipStream_t s);
-// The giant's anchor for the next map, picked on the device among ranks [0, B0lim) (the
-// component holding most of an even sample; see sheep_kernels.hip), written to *anc_out (INV
-// when B0lim = 0); gbits (nullable): the bitmap is then rebased on it (*gx_rd -> *gx_wr).
-void launch_kb_pick(const uint32_t* uf, uint32_t B0lim, const uint32_t* anc_prev, uint32_t* anc_out,
-                    uint32_t* gbits, uint32_t n_seq, const uint32_t* gx_rd, uint32_t* gx_wr,
-                    hipStream_t s);
-// refresh: re-resolve the kept starts against the current union-find first (pipelined loop).
-// gbits / gx: the giant bitmap and the slot written by the latest rebase on this stream.
-void launch_kb_apply(bool nonempty, uint32_t B0, uint32_t B1, uint32_t anchor, uint32_t* uf,
-                     uint32_t* label, uint32_t* parent, uint32_t* jump, uint64_t* kept,
-                     uint32_t* linked, uint32_t* bitmap, uint32_t* spq, uint32_t* counters,
-                     bool refresh, bool stats, unsigned long long* st, uint32_t* gbits,
-                     const uint32_t* gx, hipStream_t s,
-                     const uint32_t* anc = nullptr /* this bucket's device anchor */,
-                     const uint32_t* anc_next = nullptr /* the next map's: its root is kept */);
 // Lockstep exchange of one bucket (sheep_ls_*): pack this rank's mark words [w0, w1] (ms u64
 // slots) and kept pairs (padded to cap) for an all-gather; unpack P such blocks into the
 // bitmap (OR) and a contiguous kept array, setting *n_kept = P * cap (kept and n_kept
@@ -318,19 +350,17 @@ void launch_ls_pack(const uint32_t* bitmap, uint32_t w0, uint32_t w1, uint32_t m
 void launch_ls_count(const uint32_t* n_kept, long long* out, hipStream_t s);
 void launch_ls_unpack(const uint64_t* recv, uint32_t P, uint32_t ms, uint32_t cap, uint32_t* bitmap,
                       uint32_t w0, uint32_t w1, uint64_t* kept, uint32_t* n_kept, hipStream_t s);
-// Split lockstep apply (P > 1; see sheep_kernels.hip): the refresh alone; G of the bucket's
-// giant into *gslot; every rank's union-find part (fold, union of the kept pairs, labels;
-// counters reset); the owner's spine + zipper over its copies (zn: n_kept, n_spine, G).
-void launch_kb_refresh(uint64_t* kept, const uint32_t* n_kept, uint32_t* uf, const uint32_t* label,
-                       uint32_t* bitmap, uint32_t B0, uint32_t anchor, uint32_t* gbits,
-                       const uint32_t* gx, const uint32_t* anc, hipStream_t s);
-void launch_ls_gslot(const uint32_t* uf, const uint32_t* label, uint32_t anchor, const uint32_t* anc,
-                     uint32_t* gslot, hipStream_t s);
-void launch_ls_fold_union_label(bool nonempty, uint32_t B0, uint32_t B1, uint32_t anchor,
-                                uint32_t* uf, uint32_t* label, const uint64_t* recv, uint32_t P,
-                                uint32_t ms, uint32_t cap, uint32_t* bitmap, uint32_t* counters,
-                                uint32_t* gbits, const uint32_t* gx, hipStream_t s,
-                                const uint32_t* anc, const uint32_t* anc_next);
+// Split lockstep apply of bucket k (P > 1; see sheep_kernels.hip): the refresh alone, over the
+// owner's copies of the pairs (kept, *n_kept) and marks (bitmap); G of the bucket's giant into
+// *gslot; every rank's union-find part (fold, union of the kept pairs in recv, labels; counters
+// reset); the owner's spine + zipper over its copies (zn: n_kept, n_spine, G).
+void launch_kb_refresh(const KbState& S, size_t k, uint64_t* kept, const uint32_t* n_kept,
+                       uint32_t* bitmap, uint32_t B0, uint32_t anchor, size_t gx_slot,
+                       hipStream_t s);
+void launch_ls_gslot(const KbState& S, size_t k, uint32_t anchor, uint32_t* gslot, hipStream_t s);
+void launch_ls_fold_union_label(const KbState& S, size_t k, uint32_t B0, uint32_t B1,
+                                uint32_t anchor, bool nonempty, const uint64_t* recv, uint32_t P,
+                                uint32_t ms, uint32_t cap, size_t gx_slot, hipStream_t s);
 void launch_ls_zip(const uint64_t* zkept, uint32_t* zn, const uint32_t* zbm, uint32_t* zspq,
                    uint32_t B0, uint32_t B1, bool has_anchor, uint32_t* parent, uint32_t* jump,
                    hipStream_t s);

@@ -3680,7 +3680,7 @@ k_kb_map(const uint64_t* __restrict__ items, uint64_t e_begin, uint64_t e_end, K
          const uint32_t* __restrict__ gx, int defer, const uint32_t* __restrict__ anc,
          const uint32_t* __restrict__ gsum, uint32_t gs_words, uint32_t gs_w0, uint32_t kept_cap) {
   extern __shared__ uint32_t s_gsum[];  // gs_words words of the giant summary (dynamic LDS)
-  if (DF >= 0) defer = DF;  // (compile-time for the one-GPU loop's deferred misses)
+  if (DF >= 0) defer = DF;  // (compile-time for the deferred misses)
   __shared__ uint32_t wbits[KM_WIN / 32];
   __shared__ uint32_t wcnt[KM_WIN / 2];
   __shared__ uint32_t woff[KM_THREADS / 64 + 1];
@@ -4024,7 +4024,7 @@ __global__ void k_gb_sum(const uint32_t* __restrict__ gbits, uint32_t nfull, uin
     gsum[q >> 5] = lane ? (uint32_t)(bal >> 32) : (uint32_t)bal;
 }
 
-void launch_gb_sum(const uint32_t* gbits, uint32_t n_seq, uint32_t* gsum, hipStream_t s) {
+static void launch_gb_sum(const uint32_t* gbits, uint32_t n_seq, uint32_t* gsum, hipStream_t s) {
   const uint32_t nwords = (n_seq + 2047) / 2048;  // the words of ranks [0, n_seq)
   if (nwords == 0) return;
   const uint32_t lanes = nwords * 32;
@@ -4058,12 +4058,11 @@ __global__ void k_gb_sweep(uint32_t* uf, uint32_t* gbits, uint32_t B0lim,
   }
 }
 
-void launch_gb_sweep(uint32_t* uf, uint32_t* gbits, uint32_t B0lim, const uint32_t* gx,
-                     hipStream_t s) {
+void launch_gb_sweep(const KbState& S, uint32_t B0lim, size_t gx_slot, hipStream_t s) {
   if (B0lim == 0) return;
   const uint32_t waves = (B0lim + 63) / 64;
   hipLaunchKernelGGL(k_gb_sweep, dim3(std::min<uint32_t>((waves + 3) / 4, 4096)), dim3(BLOCK), 0, s,
-                     uf, gbits, B0lim, gx);
+                     S.uf, S.gbits, B0lim, (const uint32_t*)S.gx_of(gx_slot));
 }
 
 // The giant's anchor, picked on the device before the map of a bucket, with nothing else
@@ -4435,10 +4434,7 @@ void launch_kb_bounds(const uint64_t* items, uint64_t n, uint32_t K_e, uint32_t 
                      items, n, K_e, K_r, n_seq, gshift, out);
 }
 
-// counters: 4 device words per bucket parity, zero before the first bucket ([1] n_linked,
-// [2] n_spine, [3] n_kept; each bucket's label kernel resets its set).  spq: (n_seq / 32 + 64)
-// words; kept: (e_end - e_begin) u64.
-//
+// kept: (e_end - e_begin) u64.
 // The anchor is a rank whose component is taken as the giant: its elimination-tree root G is
 // found when the map starts (marks) and again when the zipper starts (spine).  Any rank whose
 // bucket has been applied before the map starts is exact: the two finds may see different
@@ -4446,14 +4442,10 @@ void launch_kb_bounds(const uint64_t* items, uint64_t n, uint32_t K_e, uint32_t 
 // anchor's component at rank B0, and an edge (a, b >= B0) may be moved to any vertex of a's
 // component at B0.  (The pipelined loop maps bucket k+1 while bucket k is applied, so it
 // anchors at the last rank of bucket k-1.)  INV: no giant (first buckets).
-// gbits / gx (nullable): the giant bitmap and the slot of its reference vertex that
-// launch_kb_pick wrote before this map.
-void launch_kb_map(const uint64_t* items, uint64_t e_begin, uint64_t e_end, uint32_t B0,
-                   uint32_t anchor, uint32_t* uf, const uint32_t* label, uint64_t* kept,
-                   uint64_t kept_cap, uint32_t* bitmap, uint32_t* counters, int gshift, uint32_t* cnt, bool stats,
-                   unsigned long long* st, const uint32_t* bins, uint32_t nb, uint32_t* gbits,
-                   const uint32_t* gx, int defer, hipStream_t s, const KbSegs* segs,
-                   const uint32_t* anc, const uint32_t* gsum) {
+void launch_kb_map(const KbState& S, size_t k, const uint64_t* items, uint64_t e_begin,
+                   uint64_t e_end, const KbSegs* segs, uint32_t B0, uint32_t anchor,
+                   uint64_t* kept, uint64_t kept_cap, int gshift, const uint32_t* bins,
+                   uint32_t nb, int defer, bool stats, hipStream_t s) {
   // segs: e_begin / e_end bound the bucket's records (the capacity of its bins)
   if (e_end <= e_begin) return;
   KbSegs sg{};
@@ -4472,38 +4464,46 @@ void launch_kb_map(const uint64_t* items, uint64_t e_begin, uint64_t e_end, uint
                        : (hub ? k_kb_map<false, true> : k_kb_map<false, false>);
   // the giant summary of the highest KM_GSUM words of ranks below B0 (the lo ends of most
   // records: a vertex is the lo end of its edges to higher-degree vertices) in dynamic LDS
+  // (the first map has no summary yet: the first rebase, before map 1, writes it)
+  const uint32_t* gsum = k >= 1 ? S.gsum : nullptr;
   const uint32_t w_end = (B0 + 2047) / 2048;
-  const uint32_t gs_words = (gsum && gx) ? std::min<uint32_t>(w_end, KM_GSUM) : 0u;
+  const uint32_t gs_words = gsum ? std::min<uint32_t>(w_end, KM_GSUM) : 0u;
   const uint32_t gs_w0 = w_end - gs_words;
   hipLaunchKernelGGL(mk, dim3(grid), dim3(KM_THREADS), gs_words * 4, s, items, e_begin, e_end, sg,
-                     B0, gshift, uf, label, kept, counters + 3, bitmap, cnt, st, anchor, bins, nb,
-                     gx ? gbits : nullptr, gx, defer, anc, gsum, gs_words, gs_w0,
+                     B0, gshift, S.uf, (const uint32_t*)S.label, kept, S.cnt_of(k) + 3, S.bm_of(k),
+                     S.hcnt, S.st, anchor, bins, nb, S.gbits, (const uint32_t*)S.gx_of(k), defer,
+                     (const uint32_t*)S.anc_of(k), gsum, gs_words, gs_w0,
                      (uint32_t)std::min<uint64_t>(kept_cap, 0xFFFFFFFFull));
 }
 
-void launch_kb_pick(const uint32_t* uf, uint32_t B0lim, const uint32_t* anc_prev, uint32_t* anc_out,
-                    uint32_t* gbits, uint32_t n_seq, const uint32_t* gx_rd, uint32_t* gx_wr,
-                    hipStream_t s) {
-  const uint32_t nwords = n_seq / 32 + 2;
-  const unsigned grid = gbits ? std::min<uint32_t>((nwords + BLOCK - 1) / BLOCK, 1024) : 1u;
-  hipLaunchKernelGGL(k_kb_pick, dim3(grid), dim3(BLOCK), 0, s, uf, B0lim, anc_prev, anc_out, gbits,
-                     nwords, gx_rd, gx_wr);
+void launch_kb_rebase(const KbState& S, size_t j, uint32_t B0lim, hipStream_t s) {
+  const uint32_t nwords = (uint32_t)S.bm_words;
+  const unsigned grid = std::min<uint32_t>((nwords + BLOCK - 1) / BLOCK, 1024);
+  // slot (j - 1) & 1 = (j + 1) & 1 holds what map j - 1 used
+  hipLaunchKernelGGL(k_kb_pick, dim3(grid), dim3(BLOCK), 0, s, (const uint32_t*)S.uf, B0lim,
+                     (const uint32_t*)S.anc_of(j + 1), S.anc_of(j), S.gbits, nwords,
+                     (const uint32_t*)S.gx_of(j + 1), S.gx_of(j));
+  if (S.gsum) launch_gb_sum(S.gbits, S.n_seq, S.gsum, s);
 }
 
 static bool kb_refresh_links() { return knobs().kb_rlink != 0; }
 
-void launch_kb_apply(bool nonempty, uint32_t B0, uint32_t B1, uint32_t anchor, uint32_t* uf,
-                     uint32_t* label, uint32_t* parent, uint32_t* jump, uint64_t* kept,
-                     uint32_t* linked, uint32_t* bitmap, uint32_t* spq, uint32_t* counters,
-                     bool refresh, bool stats, unsigned long long* st, uint32_t* gbits,
-                     const uint32_t* gx, hipStream_t s, const uint32_t* anc,
-                     const uint32_t* anc_next) {
+void launch_kb_apply(const KbState& S, size_t k, uint32_t B0, uint32_t B1, uint32_t anchor,
+                     bool nonempty, uint64_t* kept, bool refresh, bool stats, size_t gx_slot,
+                     hipStream_t s) {
   const uint32_t ps = 2;  // parent[2v], hint[2v + 1] (k_pj_init)
   const uint32_t scan_limit = 64;  // spine scan: bitmap words per search
+  uint32_t *uf = S.uf, *label = S.label, *parent = S.parent(), *jump = S.jump();
+  uint32_t *linked = S.linked, *bitmap = S.bm_of(k), *spq = S.spq_of(k), *gbits = S.gbits;
+  uint32_t* counters = S.cnt_of(k);
   uint32_t* n_linked = counters + 1;
   uint32_t* n_spine = counters + 2;
   uint32_t* n_kept = counters + 3;
-  if (!gx) gbits = nullptr;
+  unsigned long long* st = S.st;
+  const uint32_t* gx = S.gx_of(gx_slot);
+  // this bucket's device anchor, and the next map's: the union keeps its root on top, so that
+  // the map running beside it sees the giant's root unchanged
+  const uint32_t *anc = S.anc_of(k), *anc_next = S.anc_of(k + 1);
   if (nonempty) {
     if (refresh)
       hipLaunchKernelGGL(k_kb_refresh, dim3(2048), dim3(BLOCK), 0, s, kept, (const uint32_t*)n_kept,
@@ -4545,12 +4545,12 @@ void launch_kb_apply(bool nonempty, uint32_t B0, uint32_t B1, uint32_t anchor, u
                      gbits, gx, ps);
 }
 
-void launch_kb_refresh(uint64_t* kept, const uint32_t* n_kept, uint32_t* uf, const uint32_t* label,
-                       uint32_t* bitmap, uint32_t B0, uint32_t anchor, uint32_t* gbits,
-                       const uint32_t* gx, const uint32_t* anc, hipStream_t s) {
-  if (!gx) gbits = nullptr;
-  hipLaunchKernelGGL(k_kb_refresh, dim3(2048), dim3(BLOCK), 0, s, kept, n_kept, uf, label, bitmap,
-                     B0, anchor, gbits, gx, anc, 1);
+void launch_kb_refresh(const KbState& S, size_t k, uint64_t* kept, const uint32_t* n_kept,
+                       uint32_t* bitmap, uint32_t B0, uint32_t anchor, size_t gx_slot,
+                       hipStream_t s) {
+  hipLaunchKernelGGL(k_kb_refresh, dim3(2048), dim3(BLOCK), 0, s, kept, n_kept, S.uf,
+                     (const uint32_t*)S.label, bitmap, B0, anchor, S.gbits,
+                     (const uint32_t*)S.gx_of(gx_slot), (const uint32_t*)S.anc_of(k), 1);
 }
 
 // ---- split lockstep apply (P ranks; sheep_capi.cpp ls_apply) ------------------------------
@@ -4632,17 +4632,17 @@ k_ls_label(uint32_t* uf, uint32_t* label, uint32_t B0, uint32_t B1, uint32_t* co
   if (blockIdx.x == 0 && threadIdx.x == 0) { counters[1] = 0; counters[2] = 0; counters[3] = 0; }
 }
 
-void launch_ls_gslot(const uint32_t* uf, const uint32_t* label, uint32_t anchor, const uint32_t* anc,
-                     uint32_t* gslot, hipStream_t s) {
-  hipLaunchKernelGGL(k_ls_gslot, dim3(1), dim3(1), 0, s, uf, label, anchor, anc, gslot);
+void launch_ls_gslot(const KbState& S, size_t k, uint32_t anchor, uint32_t* gslot, hipStream_t s) {
+  hipLaunchKernelGGL(k_ls_gslot, dim3(1), dim3(1), 0, s, (const uint32_t*)S.uf,
+                     (const uint32_t*)S.label, anchor, (const uint32_t*)S.anc_of(k), gslot);
 }
 
-void launch_ls_fold_union_label(bool nonempty, uint32_t B0, uint32_t B1, uint32_t anchor,
-                                uint32_t* uf, uint32_t* label, const uint64_t* recv, uint32_t P,
-                                uint32_t ms, uint32_t cap, uint32_t* bitmap, uint32_t* counters,
-                                uint32_t* gbits, const uint32_t* gx, hipStream_t s,
-                                const uint32_t* anc, const uint32_t* anc_next) {
-  if (!gx) gbits = nullptr;
+void launch_ls_fold_union_label(const KbState& S, size_t k, uint32_t B0, uint32_t B1,
+                                uint32_t anchor, bool nonempty, const uint64_t* recv, uint32_t P,
+                                uint32_t ms, uint32_t cap, size_t gx_slot, hipStream_t s) {
+  uint32_t *uf = S.uf, *label = S.label, *bitmap = S.bm_of(k), *counters = S.cnt_of(k);
+  uint32_t* gbits = S.gbits;
+  const uint32_t *gx = S.gx_of(gx_slot), *anc = S.anc_of(k), *anc_next = S.anc_of(k + 1);
   const uint32_t anchor_next = B0 > 0 ? B0 - 1 : INV;
   if (nonempty) {
     if (anchor != INV && B1 > B0)  // the marked ranks go under the anchor's root (no forest)

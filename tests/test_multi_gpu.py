@@ -137,6 +137,22 @@ def test_multi_local_front_half_options(oracle, gpu, options, env):
     check(oracle, uv_d.cpu().numpy().view(np.uint32), 0, *out)
 
 
+@pytest.mark.parametrize("P,env", [(2, {"ls_split": 0, "kb_rlink": 0}),  # the replicated apply
+                                   (1, {"kb_rlink": 0})])                # the solo apply
+def test_multi_local_apply_without_refresh_links(oracle, gpu, options, P, env):
+    """The multi-rank driver's whole-bucket applies (both refresh the kept starts first) with the
+    refresh leaving every pair to the zipper: the same tree (R-MAT 16: 2^20 records, several
+    buckets, a giant with an anchor)."""
+    import torch
+    from sheep_amd import device
+
+    options(**env)
+    uv_d = device.rmat(16, 16, 15)
+    torch.cuda.synchronize()
+    out = device.graph2tree_multi_local(shards_of(uv_d, P), 1 << 16)
+    check(oracle, uv_d.cpu().numpy().view(np.uint32), 0, *out)
+
+
 def test_multi_local_one_rank_overflows(oracle, gpu):
     """Only one rank's direct bins overflow (its shard holds the records with the highest hi,
     far beyond its share of the global estimate): that rank groups its records through the
