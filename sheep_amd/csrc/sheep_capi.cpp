@@ -366,7 +366,7 @@ static bool degree_dev(Ctx& c, const uint32_t* d_uv, uint64_t m, uint32_t n_ids,
     if (stats) launch_deg_stats(d_deg, n_ids, stats, s);
     return false;
   }
-  if (2 * m >= (1ull << 32) && fh_tmp_words(m, n_ids) > 1) {
+  if (2 * m >= (1ull << 32) && degb_ok(n_ids)) {
     // beyond the endpoint array's u32 offsets: the fused pass, whose offsets count records
     // (it also writes the records grouped by y bucket, into scratch here)
     require_records(m, "degree");
@@ -379,8 +379,8 @@ static bool degree_dev(Ctx& c, const uint32_t* d_uv, uint64_t m, uint32_t n_ids,
     return false;
   }
   // (ids beyond 2^26: launch_degree_bucketed takes the global-atomic pass, no offsets)
-  if (degb_tmp_words(m, n_ids, nullptr, nullptr) > 1) require_endpoints(m, "degree");
-  uint32_t* tmp = (uint32_t*)c.scratch.get("degb_tmp", degb_tmp_words(m, n_ids, nullptr, nullptr) * 4);
+  if (degb_ok(n_ids)) require_endpoints(m, "degree");
+  uint32_t* tmp = (uint32_t*)c.scratch.get("degb_tmp", degb_tmp_words(m, n_ids) * 4);
   uint32_t* yhist = want_yhist ? (uint32_t*)c.scratch.get("part_ws", PART_WS_WORDS * 4) : nullptr;
   return launch_degree_bucketed(d_uv, m, n_ids, mode, d_deg, d_selfc, c.d_err, tmp, s, yhist,
                                 counted, stats);
@@ -491,10 +491,9 @@ static Front front_half(Ctx& c, const char* items_slot, const uint32_t* d_uv, ui
   const bool part = m > 0 && use_part(m);
   const bool bucketed = knobs().degree != 1;
   const bool caps_ok = bucketed && m >= (1ull << 25) && knobs().bin_direct && part_p6_ok(n_ids) &&
-                       degs_tmp_words(m, n_ids) > 1;
+                       degb_ok(n_ids);
   enum { IN_LINE, BESIDE, SAMPLED, COUNTED_FUSED, SAMPLED_FUSED } v = IN_LINE;
-  if (part && bucketed && n_ids > 0 && (ov == 3 || 2 * m >= (1ull << 32)) &&
-      fh_tmp_words(m, n_ids) > 1) {
+  if (part && bucketed && n_ids > 0 && (ov == 3 || 2 * m >= (1ull << 32)) && degb_ok(n_ids)) {
     v = COUNTED_FUSED;
   } else if (part && ov == 4 && caps_ok && front_fused_ok(m, n_ids)) {
     v = SAMPLED_FUSED;

@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "front_layout.h"
+
 namespace sheep {
 
 constexpr uint32_t INV = 0xFFFFFFFFu;
@@ -103,7 +105,9 @@ Ctx& ctx();  // this thread's context for the current device (sheep_gpu_init)
 void launch_degree(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file_mode, uint32_t* deg,
                    uint32_t* selfc, uint32_t* err, hipStream_t s);
 // Bucketed LDS degree histogram for large m (same result as launch_degree); selfc nullable.
-size_t degb_tmp_words(uint64_t m, uint32_t n_ids, int* SH_out, uint32_t* NB_out);
+// (tmp: degb_layout, front_layout.h; applicable where degb_ok(n_ids), else 1 word and the
+// global-atomic pass)
+size_t degb_tmp_words(uint64_t m, uint32_t n_ids);
 // yhist (nullable, 1024 words): also counts the y digits of launch_part_gather's first pass
 // (n_rank = n_ids), so that pass needs no counting read; returns true when it did.
 bool launch_degree_bucketed(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file_mode,
@@ -114,7 +118,7 @@ bool launch_degree_bucketed(const uint32_t* uv, uint64_t m, uint32_t n_ids, int 
 // Fused front half (graph2tree_dev): degrees (deg, selfc, stats as launch_degree_bucketed)
 // and the records (x, y) grouped by y bucket into recs (m u64), the x digits of
 // launch_part_second counted into part_ws (spread, xh_ix) — what launch_part_first produced.  tmp:
-// fh_tmp_words (1: not applicable, n_ids beyond 2^26).  False when not applicable.
+// fh_tmp_words (fh_layout, front_layout.h).  False when not applicable (degb_ok(n_ids)).
 size_t fh_tmp_words(uint64_t m, uint32_t n_ids);
 bool launch_fh_front(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file_mode, uint32_t* deg,
                      uint32_t* selfc, uint32_t* err, uint32_t* tmp, uint64_t* recs,
@@ -123,8 +127,7 @@ bool launch_fh_front(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file_mo
                      void* mark_arg = nullptr);
 void launch_deg_stats(const uint32_t* deg, uint32_t n, uint32_t* stats /*[0]=max,[1]=zeros*/,
                       hipStream_t s);
-// Exclusive scan of n u32 (n < 2^32); tmp needs scan_tmp_words(n) u32.
-size_t scan_tmp_words(uint64_t n);
+// Exclusive scan of n u32 (n < 2^32); tmp needs scan_tmp_words(n) u32 (front_layout.h).
 void launch_scan_exclusive(const uint32_t* in, uint32_t* out, uint64_t n, uint32_t* tmp,
                            hipStream_t s);
 size_t rsort_tmp_words(uint64_t n);
@@ -186,12 +189,8 @@ uint64_t* group_by_bins(const uint32_t* uv, bool pre, uint64_t m, const uint32_t
 // tile, ~134 M a call at RMAT-26, performed at the memory side) are spread over memory: cursor
 // q sits at u64 index fs_cix(q) = (q / 8) * SHEEP_FS_CLS + q % 8, eight to a 64-B line and
 // consecutive lines SHEEP_FS_CLS u64 apart (8: contiguous).
-#ifndef SHEEP_FS_CLS
-#define SHEEP_FS_CLS 64
-#endif
-constexpr uint32_t FS_CLS = SHEEP_FS_CLS;
+// (FS_CLS and fs_cur_words, the cursors' words: front_layout.h)
 __host__ __device__ inline uint32_t fs_cix(uint32_t q) { return (q >> 3) * FS_CLS + (q & 7u); }
-constexpr size_t fs_cur_words(uint32_t n) { return 2 * (size_t)((n + 7) / 8) * FS_CLS; }
 // (+ the fused front pass's subregion tables: 8192 u64 starts + 2, cursors (spread), ends, u32
 // tile map)
 // The second partition pass's x-digit counts (256 u32, added to by every tile of the first pass
@@ -224,10 +223,9 @@ void launch_part_second(const uint64_t* mid, uint64_t m, const uint32_t* rank, u
 // y regions go to part_ws for launch_part_first_caps (mid_slots records; the event caps_done
 // marks them written).  *ovf is set when a run outgrew its region: the degrees
 // are then invalid and the caller runs the exact pass.  False when not applicable.
+// tmp: degs_tmp_words (degs_layout, front_layout.h: the sampled view; the fused pass below takes
+// the same slot by its fused view).
 size_t degs_tmp_words(uint64_t m, uint32_t n_ids);
-// The most slots the sampled capacity regions of `items` items over n_regions can take (the
-// first pass's packed records: fs_room(m, 1024) slots of 6 bytes).
-uint64_t fs_room(uint64_t items, uint32_t n_regions);
 bool launch_degree_sampled(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file_mode,
                            uint32_t* deg, uint32_t* selfc, uint32_t* err, uint32_t* tmp,
                            uint32_t* part_ws, uint64_t mid_slots, uint32_t* stats, uint32_t* ovf,

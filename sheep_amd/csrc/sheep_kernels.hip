@@ -283,14 +283,7 @@ __global__ void k_scan_down(const uint32_t* __restrict__ in, uint32_t* __restric
   }
 }
 
-size_t scan_tmp_words(uint64_t n) {
-  size_t words = 0;
-  while (n > (uint64_t)TILE) {
-    n = (n + TILE - 1) / TILE;
-    words += n;
-  }
-  return words + 1;
-}
+static_assert(TILE == SCAN_TILE, "scan_tmp_words (front_layout.h) counts this scan's tiles");
 
 void launch_scan_exclusive(const uint32_t* in, uint32_t* out, uint64_t n, uint32_t* tmp,
                            hipStream_t s) {
@@ -312,16 +305,17 @@ void launch_scan_exclusive(const uint32_t* in, uint32_t* out, uint64_t n, uint32
 // MI355X (k_degree above: 95 ms for RMAT-26's 2.1 G endpoints), so endpoints are first
 // partitioned by id range into NB <= 1024 buckets of 2^SH <= 65536 ids, written as 16-bit
 // local ids, then counted in LDS:
-//   k_degb_count    per-chunk bucket counts -> counts[bucket][chunk] (digit-major, scanned)
+//   k_degb_count    per-chunk bucket counts -> counts[chunk][bucket] (tile-major, tm_offsets)
 //   k_degb_scatter  block-local counting sort of the chunk in LDS (its counts come from
 //                   k_degb_count), then each wave writes whole bucket runs (~128 B at RMAT-26);
 //                   self-loop records also bump selfc[v] (global atomics: self-loops are rare)
-//   k_degb_hist     one workgroup per (bucket, half of its id range <= 32768 ids): LDS
+//   k_degb_hist     one workgroup per bucket (<= 32768 ids; k_degb_hist16 for 65536): LDS
 //                   counters, wave-level aggregation of repeated ids (hubs), coalesced write
 // LLAMA mode emits t, and h only when t != h; FILE mode emits both.
 // Supports n_ids <= 2^26 (launch_degree_bucketed falls back to k_degree above that).
+// The constants the passes' scratch layouts depend on (DEGB_THREADS, DEGB_CHUNK, DEGB_NB, TM_G,
+// PD_Y, FF_GMAX, FS_MAX, FS_STRIDE) and the layouts themselves: front_layout.h.
 // ---------------------------------------------------------------------------------------
-static constexpr int DEGB_THREADS = 1024;
 // A record streamed once (non-temporal: it should not evict what the other kernels keep).
 __device__ __forceinline__ uint2 ld_rec_nt(const uint2* p) {
   const uint64_t v = __builtin_nontemporal_load((const uint64_t*)p);
@@ -351,13 +345,9 @@ __device__ __forceinline__ void deg_stats_flush(uint32_t* stats, uint32_t mx, ui
   }
 }
 // Tile-major count matrices and their scan (defined with the hi bins below).
-static constexpr uint32_t TM_G = 256;  // tiles per group
 static void tm_offsets(const uint32_t* counts, uint32_t* offsets, uint32_t ntiles, uint32_t NC,
                        uint32_t nb, uint32_t* gsum, unsigned long long* bin_start, hipStream_t s,
                        uint32_t G = TM_G);
-static constexpr int DEGB_CHUNK = 32768;  // edges per chunk (<= 65536 endpoints -> 128 KB LDS)
-static constexpr uint32_t DEGB_NB = 1024;
-static constexpr uint32_t DEGB_HALF = 32768;  // ids counted by one hist workgroup
 
 // Digits of the partition passes of the rank gathers (launch_part_gather): the first pass
 // (by y) cuts the ids into 1024 ranges (256 KB rank slices for the second pass's gathers), the
@@ -365,7 +355,7 @@ static constexpr uint32_t DEGB_HALF = 32768;  // ids counted by one hist workgro
 // 8.2 -> 7.7 ms but the second pass 5.6 -> 8.0 ms, its 8K-record tiles then writing 64-B
 // runs).  part_ws layout (PART_WS_WORDS u32): y-digit counts [0, 1024), (unused to 1280), u64
 // cursors from word 1280; the x-digit counts are spread at PW_XH (below).
-static constexpr uint32_t PD_Y = 1024, PD_X = 256, PW_CUR = 1280;  // (words 1024-1279: unused)
+static constexpr uint32_t PD_X = 256, PW_CUR = 1280;  // (PD_Y = 1024; words 1024-1279: unused)
 // ...then the u32 region starts of both passes' outputs, the second pass's u64 cursors (the
 // first pass's stay: they are its regions' fill) and the first pass's capacity region ends.
 static constexpr uint32_t PW_YST = 1280 + 2 * 1024, PW_XST = PW_YST + PD_Y + 1;
@@ -374,7 +364,6 @@ static_assert(PW_XCUR % 2 == 0 && PW_YCAP % 2 == 0, "u64 arrays");
 // ...then the fused front pass's y subregions (k_front_fused, FF_GMAX tile groups at most): u64
 // starts (FS_MAX + 1), cursors and ends (FS_MAX each), and the u32 first tile of each subregion
 // in the second pass's tile map (FS_MAX + 1; k_fs_tile_scan).
-static constexpr uint32_t FF_GMAX = 8, FS_MAX = DEGB_NB * FF_GMAX;
 static constexpr uint32_t PW_FST = PW_YCAP + 2 * PD_Y, PW_FCUR = PW_FST + 2 * (FS_MAX + 2),
                           PW_FCAP = PW_FCUR + (uint32_t)fs_cur_words(FS_MAX),
                           PW_FTOFF = PW_FCAP + 2 * FS_MAX;
@@ -467,8 +456,8 @@ __device__ __forceinline__ uint32_t tile_digit(const uint32_t* sst, uint64_t pos
 
 __global__ void __launch_bounds__(DEGB_THREADS)
 k_degb_count(const uint2* __restrict__ uv, uint64_t m, uint32_t n_ids, int file_mode, int SH,
-             uint32_t NB, uint32_t* __restrict__ counts, uint32_t nchunks, uint32_t* err,
-             int psh, uint32_t* __restrict__ yhist, int tm) {
+             uint32_t NB, uint32_t* __restrict__ counts /* tile-major: [chunk][bucket] */,
+             uint32_t* err, int psh, uint32_t* __restrict__ yhist) {
   __shared__ uint32_t hist[DEGB_NB];
   __shared__ uint32_t yh[PD_Y];  // y digits of the later rank-gather partition (nullable yhist)
   for (uint32_t i = threadIdx.x; i < NB; i += blockDim.x) hist[i] = 0;
@@ -499,13 +488,13 @@ k_degb_count(const uint2* __restrict__ uv, uint64_t m, uint32_t n_ids, int file_
     for (uint32_t i = threadIdx.x; i < PD_Y; i += blockDim.x)
       if (yh[i]) atomicAdd(&yhist[i], yh[i]);
   for (uint32_t i = threadIdx.x; i < NB; i += blockDim.x)
-    counts[tm ? (uint64_t)blockIdx.x * NB + i : (uint64_t)i * nchunks + blockIdx.x] = hist[i];
+    counts[(uint64_t)blockIdx.x * NB + i] = hist[i];
 }
 
 __global__ void __launch_bounds__(DEGB_THREADS)
 k_degb_scatter(const uint2* __restrict__ uv, uint64_t m, uint32_t n_ids, int file_mode, int SH,
                uint32_t NB, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets,
-               uint32_t nchunks, uint16_t* __restrict__ ep, uint32_t* __restrict__ selfc, int tm) {
+               uint16_t* __restrict__ ep, uint32_t* __restrict__ selfc) {
   __shared__ uint32_t cur[DEGB_NB], start[DEGB_NB], goff[DEGB_NB], wsum[DEGB_THREADS / 64];
   __shared__ uint16_t buf[2 * DEGB_CHUNK];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -513,7 +502,7 @@ k_degb_scatter(const uint2* __restrict__ uv, uint64_t m, uint32_t n_ids, int fil
   // this chunk's bucket counts and global run offsets (one scattered read per thread)
   uint32_t cnt = 0;
   if (t < (int)NB) {
-    const uint64_t at = tm ? (uint64_t)blockIdx.x * NB + t : (uint64_t)t * nchunks + blockIdx.x;
+    const uint64_t at = (uint64_t)blockIdx.x * NB + t;
     cnt = counts[at];
     goff[t] = offsets[at];
   }
@@ -568,7 +557,6 @@ k_degb_scatter(const uint2* __restrict__ uv, uint64_t m, uint32_t n_ids, int fil
 // pass reserves on the digit cursors (k_part, cap_end).  A run that would cross its region's
 // end is dropped and a flag set: the caller then runs the exact (counted) pass instead.  The
 // regions and the fill are all the readers see, so any capacities give the same degrees.
-static constexpr uint32_t FS_STRIDE = 256;
 
 // FF_G (k_front_fused): the groups of tiles whose runs of one region go to a subregion of
 // their own (group = tile % G; see k_front_fused).  The sample counts each group's records
@@ -608,15 +596,12 @@ k_front_sample(const uint2* __restrict__ uv, uint64_t m, uint32_t n_ids, int fil
 // sigma (sigma = sqrt(FS_STRIDE * est), the sampling error) + 2048, at most lim.  A region
 // outgrows it with probability ~3e-7 on an unordered stream.  Over n regions the capacities
 // sum to at most E + 5 sqrt(FS_STRIDE n E) + 2048 n (Cauchy-Schwarz), E = the sampled total
-// <= 2 (m + FS_STRIDE) endpoints or m + FS_STRIDE records: fs_room sizes the buffers by it.
+// <= 2 (m + FS_STRIDE) endpoints or m + FS_STRIDE records: fs_room (front_layout.h) sizes the
+// buffers by it.
 __device__ __forceinline__ unsigned long long fs_cap(uint32_t c, unsigned long long lim) {
   const double est = (double)c * FS_STRIDE;
   const double cap = est + 5.0 * sqrt((double)FS_STRIDE * est) + 2048.0;
   return cap < (double)lim ? (unsigned long long)cap : lim;
-}
-uint64_t fs_room(uint64_t items, uint32_t n_regions) {
-  const double e = (double)items + 2.0 * FS_STRIDE;
-  return (uint64_t)(e + 5.0 * std::sqrt((double)FS_STRIDE * n_regions * e)) + 2049ull * n_regions + 64;
 }
 
 // One block of 1024 threads: bucket regions (bst: NB + 1 starts, bcur: cursors = starts, bcap:
@@ -919,36 +904,30 @@ k_front_fused(const uint2* __restrict__ uv, uint64_t m, uint32_t n_ids, int file
 }
 
 __global__ void __launch_bounds__(DEGB_THREADS, 8)  // (8 waves per SIMD, two blocks per CU: <= 64 VGPRs)
-k_degb_hist(const uint16_t* __restrict__ ep, const uint32_t* __restrict__ offsets,
-            const uint32_t* __restrict__ counts, uint32_t nchunks, uint32_t NB, int SH, uint32_t H,
-            uint32_t n_ids, uint32_t* __restrict__ deg, const unsigned long long* __restrict__ bstart,
-            uint32_t* __restrict__ stats, int plain, const uint16_t* __restrict__ ep2 = nullptr,
-            const unsigned long long* __restrict__ bstart2 = nullptr,
-            const uint64_t* __restrict__ rec0 = nullptr,
-            const unsigned long long* __restrict__ bend = nullptr /* capacity regions' fill */,
-            const unsigned long long* __restrict__ bend2 = nullptr /* ... of ep2's regions */,
-            uint32_t G = 1, int spread = 0 /* bend / bend2 at fs_cix (k_front_fused's cursors) */) {
+k_degb_hist(const uint16_t* __restrict__ ep, int SH, uint32_t n_ids, uint32_t* __restrict__ deg,
+            const unsigned long long* __restrict__ bstart, uint32_t* __restrict__ stats,
+            const uint16_t* __restrict__ ep2, const unsigned long long* __restrict__ bstart2,
+            const uint64_t* __restrict__ rec0,
+            const unsigned long long* __restrict__ bend /* nullable: capacity regions' fill */,
+            const unsigned long long* __restrict__ bend2 /* ... of ep2's regions */, uint32_t G,
+            int spread /* bend / bend2 at fs_cix (k_front_fused's cursors) */) {
   // span words of dynamic LDS (degb_hist_lds): 16 KB for R-MAT-22's 4096-id buckets, where a
   // fixed 128 KB array held the CU to one block
   extern __shared__ uint32_t cnt[];
-  const uint32_t b = blockIdx.x / H, h = blockIdx.x % H;
-  const uint32_t span = H > 1 ? DEGB_HALF : (1u << SH);
+  const uint32_t b = blockIdx.x;
+  const uint32_t span = 1u << SH;
   for (uint32_t i = threadIdx.x; i < span; i += blockDim.x) cnt[i] = 0;
   block_sync();
   const int lane = threadIdx.x & 63;
-  // ep2 (nullable, tile-major bstart2): a second endpoint array (the fused front half's x ids)
-  // G > 1 (with bstart): the bucket's entries lie in G subregions (k_front_fused's groups)
+  // ep2 (nullable, bstart2): a second endpoint array (the fused front half's x ids)
+  // G > 1: the bucket's entries lie in G subregions (k_front_fused's groups)
   for (uint32_t sq = 0; sq < (ep2 ? 2u : 1u) * G; ++sq) {
   const int sg = (int)(sq / G);
   const uint32_t bq = b * G + sq % G;  // the bucket's subregion (G = 1: the bucket)
   const uint16_t* __restrict__ ep_s = sg ? ep2 : ep;
-  // bstart (tile-major counts): bucket starts and the total; else the digit-major offsets
-  const uint64_t last = (uint64_t)NB * nchunks - 1;
-  uint64_t s0 = sg ? bstart2[bq] : bstart ? bstart[bq] : offsets[(uint64_t)b * nchunks];
-  uint64_t s1 = sg ? bstart2[bq + 1]
-                   : bstart ? bstart[bq + 1]
-                            : (b + 1 < NB) ? offsets[(uint64_t)(b + 1) * nchunks]
-                                           : (uint64_t)offsets[last] + counts[last];
+  // bucket (subregion) starts, then the total
+  uint64_t s0 = sg ? bstart2[bq] : bstart[bq];
+  uint64_t s1 = sg ? bstart2[bq + 1] : bstart[bq + 1];
   const uint32_t cq = spread ? fs_cix(bq) : bq;
   if (bend && sg == 0) s1 = min(s1, (uint64_t)bend[cq]);  // (a region's fill past its end: dropped)
   if (bend2 && sg == 1) s1 = min(s1, (uint64_t)bend2[cq]);
@@ -962,10 +941,8 @@ k_degb_hist(const uint16_t* __restrict__ ep, const uint32_t* __restrict__ offset
         q[u] = i < s1 ? ld_rec_nt((const uint2*)rec0 + i) : make_uint2(0, INV);
       }
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const uint32_t e = q[u].y & lm;
-        if (q[u].y != INV && (H == 1 || (e >> 15) == h)) atomicAdd(&cnt[H > 1 ? (e & (DEGB_HALF - 1)) : e], 1u);
-      }
+      for (int u = 0; u < 8; ++u)
+        if (q[u].y != INV) atomicAdd(&cnt[q[u].y & lm], 1u);
     }
     continue;
   }
@@ -998,13 +975,9 @@ k_degb_hist(const uint16_t* __restrict__ ep, const uint32_t* __restrict__ offset
       for (int k = 0; k < 8; ++k) {
         uint64_t ik = i + k;
         uint32_t e = (wv[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
-        bool done = !(ik >= s0 && ik < s1) || (H > 1 && (e >> 15) != h);
+        bool done = !(ik >= s0 && ik < s1);
         // (masked: a capacity region's unwritten hole, read only on the way to the exact pass)
-        uint32_t v = H > 1 ? (e & (DEGB_HALF - 1)) : (e & (span - 1));
-        if (plain) {  // as k_degb_hist16
-          if (!done) atomicAdd(&cnt[v], 1u);
-          continue;
-        }
+        uint32_t v = e & (span - 1);
         // one round of leader matching folds a hub's repeated id into one LDS add
         uint64_t act = __ballot(!done);
         if (act) {
@@ -1020,7 +993,7 @@ k_degb_hist(const uint16_t* __restrict__ ep, const uint32_t* __restrict__ offset
   }
   }  // segments
   block_sync();
-  uint64_t g0 = ((uint64_t)b << SH) + (uint64_t)h * span;
+  uint64_t g0 = (uint64_t)b << SH;
   uint32_t mx = 0, zeros = 0, big = 0;
   for (uint32_t i = threadIdx.x; i < span; i += blockDim.x)
     if (g0 + i < n_ids) {
@@ -1033,43 +1006,33 @@ k_degb_hist(const uint16_t* __restrict__ ep, const uint32_t* __restrict__ offset
   if (stats) deg_stats_flush(stats, mx, zeros, big);
 }
 
-// Dynamic LDS of k_degb_hist: its counters, one word per id of a bucket (or of a half).
-static size_t degb_hist_lds(int SH, uint32_t H) {
-  return (size_t)(H > 1 ? DEGB_HALF : (1u << SH)) * 4;
-}
+// Dynamic LDS of k_degb_hist: its counters, one word per id of a bucket.
+static size_t degb_hist_lds(int SH) { return (size_t)(1u << SH) * 4; }
 
-// Buckets of 65536 ids (n_ids > 2^25): one workgroup per bucket reads the bucket's run ONCE
-// (k_degb_hist needs two workgroups there, each reading the whole run for its half).  The
+// Buckets of 65536 ids (n_ids > 2^25): one workgroup per bucket (u32 counters for them all
+// would not fit the LDS: k_degb_hist once ran two workgroups there, each reading the whole run
+// for its half of the ids).  The
 // 65536 counters are u16 halves of 32768 LDS words; the run is counted in segments of at most
 // 65535 entries, so no half can carry into its neighbour, and after each segment every thread
 // folds its 64 ids into u32 registers.
 __global__ void __launch_bounds__(DEGB_THREADS)
-k_degb_hist16(const uint16_t* __restrict__ ep, const uint32_t* __restrict__ offsets,
-              const uint32_t* __restrict__ counts, uint32_t nchunks, uint32_t NB, uint32_t n_ids,
-              uint32_t* __restrict__ deg, const unsigned long long* __restrict__ bstart,
-              uint32_t* __restrict__ stats, int plain, const uint16_t* __restrict__ ep2 = nullptr,
-              const unsigned long long* __restrict__ bstart2 = nullptr,
-              const uint64_t* __restrict__ rec0 = nullptr,
-              const unsigned long long* __restrict__ bend = nullptr /* capacity regions' fill */,
-              const unsigned long long* __restrict__ bend2 = nullptr /* ... of ep2's regions */) {
+k_degb_hist16(const uint16_t* __restrict__ ep, uint32_t n_ids, uint32_t* __restrict__ deg,
+              const unsigned long long* __restrict__ bstart, uint32_t* __restrict__ stats,
+              const uint16_t* __restrict__ ep2, const unsigned long long* __restrict__ bstart2,
+              const uint64_t* __restrict__ rec0,
+              const unsigned long long* __restrict__ bend /* nullable: capacity regions' fill */) {
   __shared__ uint32_t pk[32768];
   const uint32_t b = blockIdx.x;
-  const int lane = threadIdx.x & 63;
   uint32_t acc[64];
 #pragma unroll
   for (int k = 0; k < 64; ++k) acc[k] = 0;
   constexpr int V = 4;
-  // ep2 (nullable, tile-major bstart2): a second endpoint array (the fused front half's x ids)
+  // ep2 (nullable, bstart2): a second endpoint array (the fused front half's x ids)
   for (int sg = 0; sg < (ep2 ? 2 : 1); ++sg) {
   const uint16_t* __restrict__ ep_s = sg ? ep2 : ep;
-  const uint64_t last = (uint64_t)NB * nchunks - 1;
-  const uint64_t s0 = sg ? bstart2[b] : bstart ? bstart[b] : offsets[(uint64_t)b * nchunks];
-  uint64_t s1 = sg ? bstart2[b + 1]
-                   : bstart ? bstart[b + 1]
-                            : (b + 1 < NB) ? offsets[(uint64_t)(b + 1) * nchunks]
-                                           : (uint64_t)offsets[last] + counts[last];
+  const uint64_t s0 = sg ? bstart2[b] : bstart[b];
+  uint64_t s1 = sg ? bstart2[b + 1] : bstart[b + 1];
   if (bend && sg == 0) s1 = min(s1, (uint64_t)bend[b]);
-  if (bend2 && sg == 1) s1 = min(s1, (uint64_t)bend2[b]);
   for (uint64_t g0 = s0; g0 < s1; g0 += 65535) {
     const uint64_t g1 = min(g0 + 65535, s1);
     for (uint32_t i = threadIdx.x; i < 32768; i += DEGB_THREADS) pk[i] = 0;
@@ -1105,21 +1068,8 @@ k_degb_hist16(const uint16_t* __restrict__ ep, const uint32_t* __restrict__ offs
         for (int k = 0; k < 8; ++k) {
           uint64_t ik = i + k;
           uint32_t v = (wv[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
-          bool done = !(ik >= g0 && ik < g1);
-          if (plain) {  // no matching: repeated ids of a wave serialise in the LDS atomic unit
-            if (!done) atomicAdd(&pk[v >> 1], 1u << (16 * (v & 1)));
-            continue;
-          }
-          // one round of leader matching folds a hub's repeated id into one LDS add
-          uint64_t act = __ballot(!done);
-          if (act) {
-            int leader = __ffsll((unsigned long long)act) - 1;
-            uint32_t lv = __builtin_amdgcn_readlane(v, leader);
-            uint64_t same = __ballot(!done && v == lv);
-            if (lane == leader) atomicAdd(&pk[lv >> 1], (uint32_t)__popcll(same) << (16 * (lv & 1)));
-            if ((same >> lane) & 1) done = true;
-            if (!done) atomicAdd(&pk[v >> 1], 1u << (16 * (v & 1)));
-          }
+          // no matching: repeated ids of a wave serialise in the LDS atomic unit
+          if (ik >= g0 && ik < g1) atomicAdd(&pk[v >> 1], 1u << (16 * (v & 1)));
         }
       }
     }
@@ -1316,43 +1266,57 @@ k_degb_hist16s(const uint16_t* __restrict__ ex, const unsigned long long* __rest
   }
 }
 
-// SH: local-id bits, NB buckets; false when n_ids is beyond the bucketed path (> 2^26).
-static bool degb_params(uint32_t n_ids, int* SH_out, uint32_t* NB_out) {
-  int bits = 0;
-  for (uint64_t v = n_ids ? n_ids - 1 : 0; v; v >>= 1) ++bits;
-  int SH = bits - 10;
-  if (SH < 0) SH = 0;
-  if (SH > 16) return false;
-  *SH_out = SH;
-  *NB_out = (uint32_t)(((uint64_t)n_ids + (1u << SH) - 1) >> SH);
-  return true;
+// The scratch of the passes below: their layouts' totals (front_layout.h), 1 word where the
+// pass does not apply (!degb_ok(n_ids)).
+size_t degb_tmp_words(uint64_t m, uint32_t n_ids) { return degb_layout(m, n_ids).total; }
+size_t degs_tmp_words(uint64_t m, uint32_t n_ids) { return degs_layout(m, n_ids).total; }
+size_t fh_tmp_words(uint64_t m, uint32_t n_ids) { return fh_layout(m, n_ids).total; }
+static_assert(PD_Y == DEGB_NB, "degs_tmp's sample counts: as many y digits as buckets");
+
+// What a bucket histogram counts, bucket by bucket: the ids of `ids` (or the y ids of the
+// records `recs` in its place) and, where given, of a second array `ids2`.  Bucket b's entries
+// of an array lie at [start[b], start[b + 1]), cut at fill[b] where the regions are capacity
+// regions (k_front_caps) filled up to their cursors; with G > 1 a bucket is G adjacent
+// subregions b * G .. b * G + G - 1, and `spread` fills are k_front_fused's cursors (fill of
+// region q at u64 index fs_cix(q)).
+struct HistSrc {
+  const uint16_t* ids = nullptr;
+  const uint64_t* recs = nullptr;
+  const unsigned long long* start = nullptr;
+  const unsigned long long* fill = nullptr;
+  const uint16_t* ids2 = nullptr;
+  const unsigned long long* start2 = nullptr;
+  const unsigned long long* fill2 = nullptr;
+  uint32_t G = 1;
+  bool spread = false;
+  uint32_t* stats = nullptr;  // nullable: max degree, zero-degree ids, ids of degree >= SEQ_BIG
+};
+// k_degb_hist16 for buckets of 65536 ids, else k_degb_hist.  (k_degb_hist16 knows one region per
+// bucket and plain fills: the fused front pass, whose fills are spread, has its own kernel
+// there, k_degb_hist16s.)
+// Each kernel has one way of adding, the one that measured faster for it; both once took either
+// as a run-time mode, and the losing modes are removed.  k_degb_hist16 adds without the per-wave
+// leader matching of repeated ids: ids are spread over 65536 counters per bucket, so a wave
+// rarely repeats one, and the match cost more than the serialised hub adds it saves (RMAT-26
+// hist 11.7 -> 10.7 ms of degree phase, twitter-shape 15.6 -> 14.1 ms).  The small-bucket
+// histogram (k_degb_hist) matches: RMAT-22's 4096-id buckets repeat hub ids within a wave
+// (degree 0.88 -> 0.94 ms with plain adds); the LJ shape would have gained from plain adds
+// (0.81 -> 0.72 ms).  Gone with them: k_degb_hist over halves of a 65536-id bucket (two
+// workgroups, each reading the whole run; k_degb_hist16 replaced it), and the digit-major count
+// matrix with its flat scan, which every kernel here could still index (the tile-major matrix
+// and tm_offsets replaced it).
+static void launch_degb_hist(const HistSrc& h, int SH, uint32_t NB, uint32_t n_ids, uint32_t* deg,
+                             hipStream_t s) {
+  if (SH > 15)
+    hipLaunchKernelGGL(k_degb_hist16, dim3(NB), dim3(DEGB_THREADS), 0, s, h.ids, n_ids, deg, h.start,
+                       h.stats, h.ids2, h.start2, h.recs, h.fill);
+  else
+    hipLaunchKernelGGL(k_degb_hist, dim3(NB), dim3(DEGB_THREADS), degb_hist_lds(SH), s, h.ids, SH,
+                       n_ids, deg, h.start, h.stats, h.ids2, h.start2, h.recs, h.fill, h.fill2, h.G,
+                       (int)h.spread);
 }
 
-static size_t degb_scan_words(uint64_t cw, uint64_t nchunks, uint32_t NB) {
-  return std::max<size_t>(scan_tmp_words(cw), NB * ((nchunks + TM_G - 1) / TM_G) + 2 * (NB + 1) + 4);
-}
-
-size_t degb_tmp_words(uint64_t m, uint32_t n_ids, int* SH_out, uint32_t* NB_out) {
-  int SH = 0;
-  uint32_t NB = 0;
-  if (!degb_params(n_ids, &SH, &NB)) return 1;
-  uint64_t nchunks = (m + DEGB_CHUNK - 1) / DEGB_CHUNK;
-  if (SH_out) *SH_out = SH;
-  if (NB_out) *NB_out = NB;
-  uint64_t cw = (uint64_t)NB * nchunks;
-  // counts, offsets, scan tmp (flat scan, or group sums + bucket starts), u16 ep (+pad)
-  return 2 * cw + degb_scan_words(cw, nchunks, NB) + (2 * m + 1) / 2 + 16;
-}
-
-// deg (and selfc if non-null) for n_ids ids; tmp sized by degb_tmp_words.
-// k_degb_hist16 adds without the per-wave leader matching of repeated ids: ids are spread over
-// 65536 counters per bucket, so a wave rarely repeats one, and the match cost more than the
-// serialised hub adds it saves (RMAT-26 hist 11.7 -> 10.7 ms of degree phase, twitter-shape
-// 15.6 -> 14.1 ms).  The small-bucket histogram (k_degb_hist) keeps the matching: RMAT-22's
-// 4096-id buckets repeat hub ids within a wave (degree 0.88 -> 0.94 ms plain); the LJ shape
-// would gain (0.81 -> 0.72 ms).
-static constexpr int DEGB_PLAIN16 = 1, DEGB_PLAIN_SMALL = 0;
-
+// deg (and selfc if non-null) for n_ids ids; tmp: degb_layout.
 bool launch_degree_bucketed(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file_mode,
                             uint32_t* deg, uint32_t* selfc, uint32_t* err, uint32_t* tmp,
                             hipStream_t s, uint32_t* yhist, hipEvent_t counted, uint32_t* stats) {
@@ -1376,53 +1340,29 @@ bool launch_degree_bucketed(const uint32_t* uv, uint64_t m, uint32_t n_ids, int 
   const int psh = part_shift(n_ids, PD_Y);  // as launch_part_gather with n_rank = n_ids
   if (yhist) (void)hipMemsetAsync(yhist, 0, PD_Y * 4, s);
   if (stats) (void)hipMemsetAsync(stats, 0, 12, s);
-  uint32_t nchunks = (uint32_t)((m + DEGB_CHUNK - 1) / DEGB_CHUNK);
-  uint64_t cw = (uint64_t)NB * nchunks;
-  uint32_t* counts = tmp;
-  uint32_t* offsets = tmp + cw;
-  uint32_t* stmp = offsets + cw;
-  uint16_t* ep = (uint16_t*)(((uintptr_t)(stmp + degb_scan_words(cw, nchunks, NB)) + 15) & ~(uintptr_t)15);
-  uint32_t H = SH > 15 ? 2u : 1u;
+  const uint32_t nchunks = (uint32_t)((m + DEGB_CHUNK - 1) / DEGB_CHUNK);
+  const DegbLayout L = degb_layout(m, n_ids);
+  uint32_t* counts = tmp + L.counts;
+  uint32_t* offsets = tmp + L.offsets;
+  unsigned long long* bstart = (unsigned long long*)(tmp + L.bstart);
+  uint16_t* ep = (uint16_t*)(tmp + L.ep);
   // tile-major counts (as the hi bins): bucket starts come from the scan
-  const int tm = 1;
-  unsigned long long* bstart = nullptr;
   hipLaunchKernelGGL(k_degb_count, dim3(nchunks), dim3(DEGB_THREADS), 0, s, (const uint2*)uv, m,
-                     n_ids, file_mode, SH, NB, counts, nchunks, err, psh, yhist, tm);
+                     n_ids, file_mode, SH, NB, counts, err, psh, yhist);
   if (counted) (void)hipEventRecord(counted, s);
-  {
-    uint32_t* gsum = stmp;
-    bstart = (unsigned long long*)(((uintptr_t)(gsum + NB * ((nchunks + TM_G - 1) / TM_G)) + 7) &
-                                   ~(uintptr_t)7);
-    tm_offsets(counts, offsets, nchunks, NB, NB, gsum, bstart, s);
-  }
+  tm_offsets(counts, offsets, nchunks, NB, NB, tmp + L.gsum, bstart, s);
   hipLaunchKernelGGL(k_degb_scatter, dim3(nchunks), dim3(DEGB_THREADS), 0, s, (const uint2*)uv, m,
-                     n_ids, file_mode, SH, NB, (const uint32_t*)counts, (const uint32_t*)offsets,
-                     nchunks, ep, selfc, tm);
-  if (H > 1)
-    hipLaunchKernelGGL(k_degb_hist16, dim3(NB), dim3(DEGB_THREADS), 0, s, (const uint16_t*)ep,
-                       (const uint32_t*)offsets, (const uint32_t*)counts, nchunks, NB, n_ids, deg,
-                       (const unsigned long long*)bstart, stats, DEGB_PLAIN16);
-  else
-    hipLaunchKernelGGL(k_degb_hist, dim3(NB * H), dim3(DEGB_THREADS), degb_hist_lds(SH, H), s, (const uint16_t*)ep,
-                       (const uint32_t*)offsets, (const uint32_t*)counts, nchunks, NB, SH, H, n_ids,
-                       deg, (const unsigned long long*)bstart, stats, DEGB_PLAIN_SMALL);
+                     n_ids, file_mode, SH, NB, (const uint32_t*)counts, (const uint32_t*)offsets, ep,
+                     selfc);
+  HistSrc h;
+  h.ids = ep;
+  h.start = bstart;
+  h.stats = stats;
+  launch_degb_hist(h, SH, NB, n_ids, deg, s);
   return yhist != nullptr;
 }
 
-// The sampled-capacity degree pass (see k_front_sample): scratch layout in u32 words.
-static uint64_t degs_ep_slots(uint64_t m, uint32_t NB) { return fs_room(2 * m, NB); }
-size_t degs_tmp_words(uint64_t m, uint32_t n_ids) {
-  int SH = 0;
-  uint32_t NB = 0;
-  if (!degb_params(n_ids, &SH, &NB)) return 1;
-  // samples (2 x FS_MAX), bucket starts / cursors / ends (u64, FS_MAX + 1 each), the u16 entries
-  // (+16-B pad): laid out for the fused pass's subregions (FF_GMAX tile groups), which holds
-  // launch_degree_sampled's smaller tables too; the fused pass's x-only entries need at most
-  // fs_room(m, FS_MAX) slots, the sampled pass's both endpoints degs_ep_slots
-  const uint64_t ep = std::max<uint64_t>(degs_ep_slots(m, NB), fs_room(m, FS_MAX));
-  return 2 * FS_MAX + 2 * 2 * ((size_t)FS_MAX + 1) + fs_cur_words(FS_MAX) + 2 + (ep + 1) / 2 + 16;
-}
-
+// The sampled-capacity degree pass (see k_front_sample); tmp: degs_layout's sampled view.
 bool launch_degree_sampled(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file_mode,
                            uint32_t* deg, uint32_t* selfc, uint32_t* err, uint32_t* tmp,
                            uint32_t* part_ws, uint64_t mid_slots, uint32_t* stats, uint32_t* ovf,
@@ -1430,39 +1370,34 @@ bool launch_degree_sampled(const uint32_t* uv, uint64_t m, uint32_t n_ids, int f
   int SH;
   uint32_t NB;
   if (m == 0 || n_ids == 0 || !degb_params(n_ids, &SH, &NB) || 2 * m >= (1ull << 32)) return false;
-  uint32_t* scnt = tmp;
-  unsigned long long* bst = (unsigned long long*)(tmp + 2 * DEGB_NB);
-  unsigned long long* bcur = bst + DEGB_NB + 1;
-  unsigned long long* bcap = bcur + DEGB_NB;
-  uint16_t* ep = (uint16_t*)(((uintptr_t)(bcap + DEGB_NB + 1) + 15) & ~(uintptr_t)15);
+  const DegsView L = degs_layout(m, n_ids).sampled;  // (stride DEGB_NB, plain cursors)
+  uint32_t* scnt = tmp + L.scnt;
+  unsigned long long* bst = (unsigned long long*)(tmp + L.bst);
+  unsigned long long* bcur = (unsigned long long*)(tmp + L.bcur);
+  unsigned long long* bcap = (unsigned long long*)(tmp + L.bcap);
+  uint16_t* ep = (uint16_t*)(tmp + L.ep);
   if (selfc) (void)hipMemsetAsync(selfc, 0, (size_t)n_ids * 4, s);
   if (stats) (void)hipMemsetAsync(stats, 0, 12, s);
-  (void)hipMemsetAsync(scnt, 0, 2 * DEGB_NB * 4, s);
+  (void)hipMemsetAsync(scnt, 0, 2 * L.stride * 4, s);
   const int psh = part_shift(n_ids, PD_Y);  // the first partition pass's y digits
   const uint64_t ns = (m + FS_STRIDE - 1) / FS_STRIDE;
   const unsigned sg = (unsigned)std::min<uint64_t>((ns + DEGB_THREADS - 1) / DEGB_THREADS, 512);
   hipLaunchKernelGGL(k_front_sample, dim3(sg), dim3(DEGB_THREADS), 0, s, (const uint2*)uv, m, n_ids,
                      file_mode, SH, NB, psh, scnt, 0, 1u, 1u);
   hipLaunchKernelGGL(k_front_caps, dim3(1), dim3(1024), 0, s, (const uint32_t*)scnt, NB, m,
-                     degs_ep_slots(m, NB), mid_slots, bst, bcur, bcap, part_ws + PW_YST,
+                     L.ep_slots, mid_slots, bst, bcur, bcap, part_ws + PW_YST,
                      (unsigned long long*)(part_ws + PW_CUR), (unsigned long long*)(part_ws + PW_YCAP),
                      (unsigned long long*)nullptr, 1u, 0);
   if (caps_done) (void)hipEventRecord(caps_done, s);
   const uint32_t nchunks = (uint32_t)((m + DEGB_CHUNK - 1) / DEGB_CHUNK);
   hipLaunchKernelGGL(k_degb_scatter_cap, dim3(nchunks), dim3(DEGB_THREADS), 0, s, (const uint2*)uv, m,
                      n_ids, file_mode, SH, NB, bcur, (const unsigned long long*)bcap, ep, selfc, ovf, err);
-  if (SH > 15)
-    hipLaunchKernelGGL(k_degb_hist16, dim3(NB), dim3(DEGB_THREADS), 0, s, (const uint16_t*)ep,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, nchunks, NB, n_ids, deg,
-                       (const unsigned long long*)bst, stats, DEGB_PLAIN16, (const uint16_t*)nullptr,
-                       (const unsigned long long*)nullptr, (const uint64_t*)nullptr,
-                       (const unsigned long long*)bcur);
-  else
-    hipLaunchKernelGGL(k_degb_hist, dim3(NB), dim3(DEGB_THREADS), degb_hist_lds(SH, 1), s, (const uint16_t*)ep,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, nchunks, NB, SH, 1u, n_ids,
-                       deg, (const unsigned long long*)bst, stats, DEGB_PLAIN_SMALL,
-                       (const uint16_t*)nullptr, (const unsigned long long*)nullptr,
-                       (const uint64_t*)nullptr, (const unsigned long long*)bcur);
+  HistSrc h;
+  h.ids = ep;
+  h.start = bst;
+  h.fill = bcur;
+  h.stats = stats;
+  launch_degb_hist(h, SH, NB, n_ids, deg, s);
   return true;
 }
 
@@ -1504,11 +1439,12 @@ bool launch_front_fused(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file
   // all of group b % G)
   unsigned grid = std::min(nt, device_cus());
   if (G > 1 && grid >= G) grid -= grid % G;
-  uint32_t* scnt = tmp;
-  unsigned long long* bst = (unsigned long long*)(tmp + 2 * FS_MAX);
-  unsigned long long* bcur = bst + FS_MAX + 1;  // (spread: fs_cix)
-  unsigned long long* bcap = bcur + fs_cur_words(FS_MAX) / 2 + 1;
-  uint16_t* ep = (uint16_t*)(((uintptr_t)(bcap + FS_MAX + 1) + 15) & ~(uintptr_t)15);
+  const DegsView L = degs_layout(m, n_ids).fused;  // (stride FS_MAX, cursors spread: fs_cix)
+  uint32_t* scnt = tmp + L.scnt;
+  unsigned long long* bst = (unsigned long long*)(tmp + L.bst);
+  unsigned long long* bcur = (unsigned long long*)(tmp + L.bcur);
+  unsigned long long* bcap = (unsigned long long*)(tmp + L.bcap);
+  uint16_t* ep = (uint16_t*)(tmp + L.ep);
   unsigned long long* ys64 = (unsigned long long*)(part_ws + PW_FST);
   unsigned long long* ycur = (unsigned long long*)(part_ws + PW_FCUR);
   unsigned long long* ycap = (unsigned long long*)(part_ws + PW_FCAP);
@@ -1523,7 +1459,7 @@ bool launch_front_fused(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file
                      file_mode, SH, NB, SH, scnt, 1, G, (uint32_t)(FF_NT * FF_IT / FS_STRIDE));
   hipLaunchKernelGGL(k_front_caps, dim3(1), dim3(1024), 0, s, (const uint32_t*)scnt, NB, m,
                      fs_room(m, NB * G), mid_slots, bst, bcur, bcap, (uint32_t*)nullptr, ycur, ycap,
-                     ys64, G, 1);
+                     ys64, G, (int)L.spread);
   if (mark) mark(mark_arg, "degree_sample");
   uint32_t* oa = (uint32_t*)mid;
   uint16_t* ob = (uint16_t*)(oa + mid_slots);
@@ -1536,6 +1472,8 @@ bool launch_front_fused(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file
   if (mark) mark(mark_arg, "front_fused");
   // the x endpoints, then the y ids (the region of y digit b is x bucket b's id range)
   if (SH > 15) {
+    // k_degb_hist16s REQUIRES spread cursors (it reads fill q at fs_cix(q)): bcur and ycur are,
+    // by this pass's view of degs_tmp (degs_layout's fused view) and by part_ws's PW_FCUR
     const uint64_t CH = hist16s_ch(m);
     const unsigned hgrid = (unsigned)(NB + (2 * m + CH - 1) / CH + 1);
     (void)hipMemsetAsync(deg, 0, (size_t)n_ids * 4, s);
@@ -1544,13 +1482,19 @@ bool launch_front_fused(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file
                        (const uint16_t*)ob, (const unsigned long long*)ys64,
                        (const unsigned long long*)ycur, NB, n_ids, CH, deg, G);
     if (stats) launch_deg_stats(deg, n_ids, stats, s);
-  } else
-    hipLaunchKernelGGL(k_degb_hist, dim3(NB), dim3(DEGB_THREADS), degb_hist_lds(SH, 1), s, (const uint16_t*)ep,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, NB, SH, 1u, n_ids,
-                       deg, (const unsigned long long*)bst, stats, DEGB_PLAIN_SMALL,
-                       (const uint16_t*)ob, (const unsigned long long*)ys64,
-                       (const uint64_t*)nullptr, (const unsigned long long*)bcur,
-                       (const unsigned long long*)ycur, G, 1);
+  } else {
+    HistSrc h;
+    h.ids = ep;
+    h.start = bst;
+    h.fill = bcur;
+    h.ids2 = ob;
+    h.start2 = ys64;
+    h.fill2 = ycur;
+    h.G = G;
+    h.spread = L.spread;
+    h.stats = stats;
+    launch_degb_hist(h, SH, NB, n_ids, deg, s);
+  }
   return true;
 }
 
@@ -1714,18 +1658,7 @@ k_fh_scatter(const uint2* __restrict__ uv, uint64_t m, uint32_t n_ids, int file_
   }
 }
 
-// Scratch of launch_fh_front (u32 words): two count and two offset matrices, the tile-major
-// scan's group sums and bucket starts for each, and the u16 x id array (16-B aligned, padded).
-size_t fh_tmp_words(uint64_t m, uint32_t n_ids) {
-  int SH = 0;
-  uint32_t NB = 0;
-  if (!degb_params(n_ids, &SH, &NB)) return 1;
-  const uint64_t nchunks = (m + DEGB_CHUNK - 1) / DEGB_CHUNK;
-  const uint64_t cw = (uint64_t)NB * nchunks;
-  const uint64_t gw = (uint64_t)NB * ((nchunks + TM_G - 1) / TM_G);
-  return 4 * cw + 2 * (gw + 2 * (NB + 1) + 8) + (m + 16) / 2 + 16;
-}
-
+// tmp: fh_layout.
 bool launch_fh_front(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file_mode, uint32_t* deg,
                      uint32_t* selfc, uint32_t* err, uint32_t* tmp, uint64_t* recs,
                      uint32_t* part_ws, uint32_t* stats, hipStream_t s,
@@ -1734,19 +1667,12 @@ bool launch_fh_front(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file_mo
   uint32_t NB;
   if (m == 0 || n_ids == 0 || !degb_params(n_ids, &SH, &NB)) return false;
   const uint32_t nchunks = (uint32_t)((m + DEGB_CHUNK - 1) / DEGB_CHUNK);
-  const uint64_t cw = (uint64_t)NB * nchunks;
-  const uint64_t gw = (uint64_t)NB * ((nchunks + TM_G - 1) / TM_G);
-  uint32_t* cy = tmp;
-  uint32_t* cx = cy + cw;
-  uint32_t* oy = cx + cw;
-  uint32_t* ox = oy + cw;
-  auto align8 = [](uint32_t* p) { return (uint32_t*)(((uintptr_t)p + 7) & ~(uintptr_t)7); };
-  uint32_t* gy = ox + cw;
-  unsigned long long* by = (unsigned long long*)align8(gy + gw);
-  uint32_t* gx = (uint32_t*)(by + NB + 2);
-  unsigned long long* bx = (unsigned long long*)align8(gx + gw);
-  auto align16 = [](void* p) { return (uint16_t*)(((uintptr_t)p + 15) & ~(uintptr_t)15); };
-  uint16_t* epx = align16(bx + NB + 2);
+  const FhLayout L = fh_layout(m, n_ids);
+  uint32_t *cy = tmp + L.cy, *cx = tmp + L.cx, *oy = tmp + L.oy, *ox = tmp + L.ox;
+  uint32_t *gy = tmp + L.gy, *gx = tmp + L.gx;
+  unsigned long long* by = (unsigned long long*)(tmp + L.by);
+  unsigned long long* bx = (unsigned long long*)(tmp + L.bx);
+  uint16_t* epx = (uint16_t*)(tmp + L.epx);
   if (selfc) (void)hipMemsetAsync(selfc, 0, (size_t)n_ids * 4, s);
   if (stats) (void)hipMemsetAsync(stats, 0, 12, s);
   (void)hipMemsetAsync(part_ws + PW_XH, 0, XH_WORDS * 4, s);  // the x digits of k_part<1>
@@ -1760,16 +1686,13 @@ bool launch_fh_front(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file_mo
                      n_ids, file_mode, SH, NB, (const uint32_t*)cx, (const uint32_t*)oy,
                      (const uint32_t*)ox, recs, epx, selfc);
   if (mark) mark(mark_arg, "degree_scatter");
-  if (SH > 15)
-    hipLaunchKernelGGL(k_degb_hist16, dim3(NB), dim3(DEGB_THREADS), 0, s, (const uint16_t*)nullptr,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, nchunks, NB, n_ids, deg,
-                       (const unsigned long long*)by, stats, DEGB_PLAIN16,
-                       (const uint16_t*)epx, (const unsigned long long*)bx, (const uint64_t*)recs);
-  else
-    hipLaunchKernelGGL(k_degb_hist, dim3(NB), dim3(DEGB_THREADS), degb_hist_lds(SH, 1), s, (const uint16_t*)nullptr,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, nchunks, NB, SH, 1u,
-                       n_ids, deg, (const unsigned long long*)by, stats, DEGB_PLAIN_SMALL,
-                       (const uint16_t*)epx, (const unsigned long long*)bx, (const uint64_t*)recs);
+  HistSrc h;
+  h.recs = recs;
+  h.start = by;
+  h.ids2 = epx;
+  h.start2 = bx;
+  h.stats = stats;
+  launch_degb_hist(h, SH, NB, n_ids, deg, s);
   return true;
 }
 

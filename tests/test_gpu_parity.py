@@ -368,6 +368,31 @@ def test_graph2tree_dev_fused_ragged_ids(oracle, gpu, n, mode):
     assert np.array_equal(w_d[:k].cpu().numpy().view(np.uint32), w)
 
 
+def test_graph2tree_dev_sampled_64k_buckets(oracle, gpu, options):
+    """The sampled degree pass (part_overlap 2: launch_degree_sampled, from 2^25 records) with
+    64K-id buckets (n_ids > 2^25): k_degb_hist16 reads each bucket's capacity region up to its
+    fill.  2^25 + 999 power-law records over 2^25 + 77 ids, FILE degrees; the sampled degrees
+    must be the ones used (neither the fused nor the exact pass ran), and seq, parent and pst
+    bit-exact."""
+    import torch
+    from sheep_amd import capi, device
+
+    options(part_overlap=2)
+    n, m, mode = (1 << 25) + 77, (1 << 25) + 999, 1
+    uv_d = device.powerlaw(n, m, 2.2, 80.0, 50)
+    s_d, p_d, w_d, k = device.graph2tree(uv_d, n, mode)
+    torch.cuda.synchronize()
+    t = dict(capi.last_timings())
+    assert "front_fused" not in t and "degree_exact" not in t
+    uv = uv_d.cpu().numpy().view(np.uint32).reshape(-1, 2)
+    seq = oracle.degree_sequence(uv, mode)
+    p, w = oracle.build_tree(uv, seq)
+    assert k == len(seq)
+    assert np.array_equal(s_d[:k].cpu().numpy().view(np.uint32), seq)
+    assert np.array_equal(p_d[:k].cpu().numpy().view(np.uint32), p)
+    assert np.array_equal(w_d[:k].cpu().numpy().view(np.uint32), w)
+
+
 @pytest.mark.parametrize("n,m,gamma,i0,seed", [(1000, 20000, 2.3, 100.0, 3),
                                                (65536, 1 << 20, 2.1, 50.0, 5),
                                                (300001, 1 << 21, 2.3, 100.0, 7)])
