@@ -1,8 +1,8 @@
-// Scratch layouts of the degree passes (sheep_kernels.hip): where each table of a pass's `tmp`
-// buffer lies, in u32 words from its start, and how many words the buffer takes.  The size
-// functions (*_tmp_words) return `total` and the launchers take their pointers from the same
-// struct, so a table cannot grow in one and not in the other.  Host code only, no HIP: plain
-// C++17 (tests/cpp/front_layout.cpp compiles it with g++).
+// Scratch layouts of the degree passes and the radix sort (sheep_kernels.hip): where each table
+// of a pass's `tmp` buffer lies, in u32 words from its start, and how many words it takes.  The
+// size functions (*_tmp_words) return `total` and the launchers take their pointers from the
+// same struct, so a table cannot grow in one and not in the other.  Host code only, no HIP:
+// plain C++17 (tests/cpp/front_layout.cpp compiles it with g++).
 // Alignment is a property of the offsets: the buffers come from hipMalloc (256-byte aligned at
 // least), u64 tables start at even words, u16 entry arrays at multiples of 4 words (16-byte
 // loads).  Every entry array keeps at least 8 entries of room behind its last entry: the
@@ -164,6 +164,24 @@ inline FhLayout fh_layout(uint64_t m, uint32_t n_ids) {
   L.bx = lay_up(L.gx + c.gw, 2);
   L.epx = lay_up(L.bx + 2 * ((size_t)NB + 2), 4);
   L.total = 4 * c.cw + 2 * (c.gw + 2 * (NB + 1) + 8) + (m + 16) / 2 + 16;
+  return L;
+}
+
+// radix_sort_u64 and group_by_bins ("rsort_tmp"): 512 digit or bin counts per tile of RS_TILE
+// items (turned into offsets in place), the tile-major scan's group sums, and 513 u64 column
+// starts (512 columns and the total).
+constexpr int RS_TILE = 8192;
+struct RsortLayout {
+  uint64_t ntiles = 0;
+  size_t counts = 0, gsum = 0, dstart = 0, total = 0;
+};
+inline RsortLayout rsort_layout(uint64_t n) {
+  RsortLayout L;
+  L.ntiles = (n + RS_TILE - 1) / RS_TILE;
+  const size_t gw = 512 * (size_t)((L.ntiles + TM_G - 1) / TM_G);
+  L.gsum = 512 * (size_t)L.ntiles;
+  L.dstart = lay_up(L.gsum + gw, 2);
+  L.total = L.gsum + gw + 2 * 513 + 4;
   return L;
 }
 

@@ -837,7 +837,7 @@ static void tree_from_sorted(Ctx& c, const uint64_t* sorted, uint64_t* spare, ui
   // giant's) root on top is harmless (ADVICE r04 noted the stale slot).
   auto apply_k = [&](size_t k, size_t slot) {
     launch_kb_apply(S, k, bk[k].first, bk[k + 1].first, anchor_of(k), recs(k) > 0,
-                    kept[S.set_of(k)], true, stats, slot, s);
+                    kept[S.set_of(k)], stats, slot, s);
   };
   if (pipe) {
     // map k+1 runs on the side stream while bucket k is applied; the rebase for map k+1 sits
@@ -1630,7 +1630,7 @@ static void ls_apply(Lockstep& L, uint32_t k, const uint64_t* d_recv, uint32_t P
       HIP_CHECK(hipStreamWaitEvent(L.zs, L.zready[z], 0));
       auto zev = L.span(L.zip_ev, L.zs);
       launch_ls_zip(L.zkept[z], L.zn[z], L.zbm[z], L.zspq, B0, B1, L.anchor(k) != INV,
-                    L.S.parent(), L.S.jump(), L.zs);
+                    L.S.parent(), L.zs);
       HIP_CHECK(hipEventRecord(zev.second, L.zs));
       HIP_CHECK(hipEventRecord(L.zdone[z], L.zs));
       L.zused[z] = true;
@@ -1641,7 +1641,7 @@ static void ls_apply(Lockstep& L, uint32_t k, const uint64_t* d_recv, uint32_t P
   } else {
     if (!solo)
       launch_ls_unpack(d_recv, P, L.ms, cap, L.S.bm_of(k), w0, w1, kept, L.S.cnt_of(k) + 3, s);
-    launch_kb_apply(L.S, k, B0, B1, L.anchor(k), L.global_e[k] > 0, kept, true, false, gslot, s);
+    launch_kb_apply(L.S, k, B0, B1, L.anchor(k), L.global_e[k] > 0, kept, false, gslot, s);
   }
   // (after the apply, before the next pick on this stream: nothing may move the bitmap's vertex
   // beside a sweep; the map of bucket k + 1 runs beside it)

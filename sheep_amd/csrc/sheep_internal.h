@@ -130,7 +130,7 @@ void launch_deg_stats(const uint32_t* deg, uint32_t n, uint32_t* stats /*[0]=max
 // Exclusive scan of n u32 (n < 2^32); tmp needs scan_tmp_words(n) u32 (front_layout.h).
 void launch_scan_exclusive(const uint32_t* in, uint32_t* out, uint64_t n, uint32_t* tmp,
                            hipStream_t s);
-size_t rsort_tmp_words(uint64_t n);
+size_t rsort_tmp_words(uint64_t n);  // rsort_layout(n).total (front_layout.h)
 int rsort_first_width(int bits);
 uint64_t* radix_sort_u64(const uint64_t* in, uint64_t* a, uint64_t* b, uint64_t n, int bit_lo,
                          int bit_hi, uint32_t* tmp, hipStream_t s, bool counted0 = false);
@@ -158,24 +158,16 @@ void launch_rank_scatter(const uint32_t* seq, uint32_t n_seq, uint32_t* rank, ui
 void launch_edge_pass_tiles(const uint32_t* uv, uint64_t m, const uint32_t* rank, uint32_t n_rank,
                             uint32_t* pst, uint64_t* items, uint32_t* err, int shift, int DB,
                             uint32_t* tmp, hipStream_t s, bool pre = false);
-// Hi bins (one-pass grouping, see sheep_kernels.hip): chunk degree sums (256 ranks per chunk),
-// the edge pass counting bins (no pst; nb <= 512 bounds, bounds[0] = 0, bounds[nb-1] = n_seq
-// so that INVALID his fall in the last bin), and the scatter by bin (bin_start: nb+1 u64).
+// Hi bins (one-pass grouping, see sheep_kernels.hip): chunk degree sums (256 ranks per chunk).
 void launch_chunk_degsum(const uint32_t* seq, const uint32_t* deg, uint32_t n_seq, uint64_t* out,
                          hipStream_t s, const uint32_t* nsd = nullptr);
-// digits: m u16 scratch (each item's bin, written by the edge pass, read by the scatter)
-void launch_edge_pass_bins(const uint32_t* uv, uint64_t m, const uint32_t* rank, uint32_t n_rank,
-                           uint64_t* items, uint32_t* err, const uint32_t* bins, uint32_t nb,
-                           uint32_t* tmp, uint16_t* digits, hipStream_t s, bool pre);
-void bin_sort_u64(const uint64_t* in, uint64_t* out, uint64_t n, const uint32_t* bins, uint32_t nb,
-                  uint32_t* tmp, unsigned long long* bin_start, const uint16_t* digits,
-                  hipStream_t s,
-                  unsigned long long* h_start = nullptr /* pinned: bin_start, before the scatter */,
-                  hipEvent_t started = nullptr /* recorded once h_start is written */);
 // Records (uv, or k_part's pre records) -> items (hi << 32 | lo) grouped by hi bin: the edge
-// pass (items, each item's bin into digits (m u16), tile bin counts), then the scatter.
+// pass counting bins (no pst; nb <= 512 bounds, bounds[0] = 0, bounds[nb-1] = n_seq so that
+// INVALID his fall in the last bin; items, each item's bin into digits (m u16), tile bin counts
+// into tmp: rsort_tmp_words(m)), then the scatter by bin.
 // Returns the buffer holding the result (items_b; items is then free); uv may be items_b.
-// bin_start, h_start, started: as bin_sort_u64.
+// bin_start: nb + 1 u64; h_start (pinned, nullable): bin_start, copied out before the scatter
+// runs; started: recorded once h_start is written.
 uint64_t* group_by_bins(const uint32_t* uv, bool pre, uint64_t m, const uint32_t* rank,
                         uint32_t n_rank, uint32_t* err, const uint32_t* bins, uint32_t nb,
                         uint64_t* items, uint64_t* items_b, uint32_t* tmp, uint16_t* digits,
@@ -280,7 +272,6 @@ struct KbState {
   // line.  The parents are copied out after the loop (launch_pj_parents).
   uint32_t* pj = nullptr;
   uint32_t* parent() const { return pj; }
-  uint32_t* jump() const { return pj + 1; }
   uint32_t* uf = nullptr;      // union-find over the ranks (iota)
   uint32_t* label = nullptr;   // a root's component's elimination-tree root (iota)
   uint32_t* linked = nullptr;  // the pre-bucket roots a zipper linked, for the bucket's union
@@ -333,12 +324,11 @@ void launch_kb_rebase(const KbState& S, size_t j, uint32_t B0lim, hipStream_t s)
 // component of the bitmap's reference vertex (slot gx_slot, as launch_kb_apply), with nothing
 // that may move that vertex running beside it.
 void launch_gb_sweep(const KbState& S, uint32_t B0lim, size_t gx_slot, hipStream_t s);
-// Apply of bucket k = ranks [B0, B1) over its kept pairs.  refresh: re-resolve the kept starts
-// against the current union-find first (the map ran beside an earlier apply).  gx_slot: the j
+// Apply of bucket k = ranks [B0, B1) over its kept pairs, whose starts it first re-resolves
+// against the current union-find (the map ran beside an earlier apply).  gx_slot: the j
 // of the latest rebase on this stream.  The union keeps the root of map k + 1's anchor on top.
 void launch_kb_apply(const KbState& S, size_t k, uint32_t B0, uint32_t B1, uint32_t anchor,
-                     bool nonempty, uint64_t* kept, bool refresh, bool stats, size_t gx_slot,
-                     hipStream_t s);
+                     bool nonempty, uint64_t* kept, bool stats, size_t gx_slot, hipStream_t s);
 // Lockstep exchange of one bucket (sheep_ls_*): pack this rank's mark words [w0, w1] (ms u64
 // slots) and kept pairs (padded to cap) for an all-gather; unpack P such blocks into the
 // bitmap (OR) and a contiguous kept array, setting *n_kept = P * cap (kept and n_kept
@@ -360,8 +350,7 @@ void launch_ls_fold_union_label(const KbState& S, size_t k, uint32_t B0, uint32_
                                 uint32_t anchor, bool nonempty, const uint64_t* recv, uint32_t P,
                                 uint32_t ms, uint32_t cap, size_t gx_slot, hipStream_t s);
 void launch_ls_zip(const uint64_t* zkept, uint32_t* zn, const uint32_t* zbm, uint32_t* zspq,
-                   uint32_t B0, uint32_t B1, bool has_anchor, uint32_t* parent, uint32_t* jump,
-                   hipStream_t s);
+                   uint32_t B0, uint32_t B1, bool has_anchor, uint32_t* parent, hipStream_t s);
 void launch_add_u32(uint32_t* p, uint64_t n, uint32_t d, hipStream_t s);  // p[i] += d (wraps)
 // Sharded degree sequence (P > 1, sheep_capi.cpp sequence_sharded; see sheep_kernels.hip).
 void launch_seq_runs(const uint64_t* sorted, uint32_t n, uint32_t* lst, uint32_t* H, hipStream_t s);

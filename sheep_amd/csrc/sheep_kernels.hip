@@ -1700,7 +1700,7 @@ bool launch_fh_front(const uint32_t* uv, uint64_t m, uint32_t n_ids, int file_mo
 // Stable LSD radix sort of packed u64 items (key = upper 32 bits), 8- or 9-bit digits.
 // Tile = 1024 threads x 8 items; wave w owns tile items [512 w, 512 w + 512), read in 8
 // rounds of 64 consecutive items (coalesced).  Per pass: k_rsort_count (tile digit
-// histograms, digit-major matrix) -> exclusive scan -> k_rsort_scatter.
+// histograms, tile-major: counts[tile * NBIN + digit]) -> tm_offsets -> k_rsort_scatter.
 // Ranking is wave-private: in each round the lanes holding one digit find each other with a
 // ballot match, and a per-wave LDS counter per digit gives the stable rank inside the wave —
 // no block barrier per round.  Then one pass over the digits turns the per-wave counts into
@@ -1720,7 +1720,7 @@ __device__ __forceinline__ uint32_t bin_of(const uint32_t* bounds, uint32_t nb, 
 
 static constexpr int RS_THREADS = 1024;
 static constexpr int RS_ITEMS = 8;
-static constexpr int RS_TILE = RS_THREADS * RS_ITEMS;
+static_assert(RS_TILE == RS_THREADS * RS_ITEMS, "rsort_layout (front_layout.h) counts these tiles");
 static constexpr int RS_WAVES = RS_THREADS / 64;
 
 // Lanes of the wave (among `valid` ones) whose digit equals this lane's d.
@@ -1736,10 +1736,9 @@ __device__ __forceinline__ uint64_t digit_match(uint32_t d, bool valid) {
   return match;
 }
 
-template <int DB, bool TM = false>  // digit bits: 8 or 9; TM: tile-major counts
+template <int DB>  // digit bits: 8 or 9
 __global__ void __launch_bounds__(RS_THREADS)
-k_rsort_count(const uint64_t* __restrict__ in, uint64_t n, int shift, uint32_t* __restrict__ counts,
-              uint32_t ntiles) {
+k_rsort_count(const uint64_t* __restrict__ in, uint64_t n, int shift, uint32_t* __restrict__ counts) {
   constexpr uint32_t NBIN = 1u << DB;
   __shared__ uint32_t hist[NBIN];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -1761,41 +1760,27 @@ k_rsort_count(const uint64_t* __restrict__ in, uint64_t n, int shift, uint32_t* 
     if (valid && (match & lt) == 0) atomicAdd(&hist[d], (uint32_t)__popcll(match));
   }
   block_sync();
-  for (uint32_t i = t; i < NBIN; i += RS_THREADS)
-    counts[TM ? (uint64_t)blockIdx.x * NBIN + i : (uint64_t)i * ntiles + blockIdx.x] = hist[i];
+  for (uint32_t i = t; i < NBIN; i += RS_THREADS) counts[(uint64_t)blockIdx.x * NBIN + i] = hist[i];
 }
 
-// TM: offsets are tile-major (offsets[tile * NBIN + digit], see k_tm_rows) instead of
-// digit-major (offsets[digit * ntiles + tile]): the tile reads its NBIN offsets as one
-// contiguous run instead of NBIN scattered words.
-template <int DB, bool BINS = false, bool TM = false>
+// offsets are tile-major (offsets[tile * NBIN + digit], see k_tm_rows): the tile reads its NBIN
+// offsets as one contiguous run.
+template <int DB>
 __global__ void __launch_bounds__(RS_THREADS)
 k_rsort_scatter(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t n, int shift,
-                const uint32_t* __restrict__ offsets, uint32_t ntiles,
-                const uint32_t* __restrict__ bins = nullptr, uint32_t nb = 0,
-                const uint16_t* __restrict__ digits = nullptr) {
+                const uint32_t* __restrict__ offsets) {
   constexpr uint32_t NBIN = 1u << DB;
   __shared__ uint64_t stage[RS_TILE];
   __shared__ uint32_t whist[RS_WAVES][NBIN];
   __shared__ uint32_t tstart[NBIN], goff[NBIN], wsum[RS_WAVES];
-  __shared__ uint32_t sb[BINS ? NBIN : 1];
-  __shared__ uint16_t stage_d[BINS ? RS_TILE : 1];  // bins: the digit of each staged item
-  auto digit = [&](uint64_t it) -> uint32_t {
-    const uint32_t hi = (uint32_t)(it >> 32);
-    return BINS ? bin_of(sb, nb, hi) : (uint32_t)(it >> (32 + shift)) & (NBIN - 1);
-  };
+  auto digit = [&](uint64_t it) -> uint32_t { return (uint32_t)(it >> (32 + shift)) & (NBIN - 1); };
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const uint64_t tbase = (uint64_t)blockIdx.x * RS_TILE;
   const uint32_t tile_n = (uint32_t)((n - tbase) < (uint64_t)RS_TILE ? (n - tbase) : RS_TILE);
   const uint32_t wbase = (uint32_t)w * (64 * RS_ITEMS) + lane;  // tile index of round 0
   const uint64_t lt = lane ? (~0ull >> (64 - lane)) : 0ull;
-  for (uint32_t i = t; i < NBIN; i += RS_THREADS)
-    goff[i] = TM ? offsets[(uint64_t)blockIdx.x * NBIN + i] : offsets[(uint64_t)i * ntiles + blockIdx.x];
+  for (uint32_t i = t; i < NBIN; i += RS_THREADS) goff[i] = offsets[(uint64_t)blockIdx.x * NBIN + i];
   for (uint32_t i = lane; i < NBIN; i += 64) whist[w][i] = 0;
-  if (BINS) {
-    for (uint32_t i = t; i < nb; i += RS_THREADS) sb[i] = bins[i];
-    block_sync();
-  }
   uint32_t dg[RS_ITEMS];
   uint64_t item[RS_ITEMS];
   uint32_t rk[RS_ITEMS];
@@ -1803,13 +1788,12 @@ k_rsort_scatter(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uin
   for (int k = 0; k < RS_ITEMS; ++k) {
     uint32_t li = wbase + (uint32_t)k * 64;
     item[k] = li < tile_n ? in[tbase + li] : 0ull;
-    if (BINS) dg[k] = li < tile_n ? digits[tbase + li] : 0u;
   }
   // stable rank inside the wave: rounds in item order, lanes in item order within a round
 #pragma unroll
   for (int k = 0; k < RS_ITEMS; ++k) {
     bool valid = wbase + (uint32_t)k * 64 < tile_n;
-    uint32_t d = BINS ? dg[k] : digit(item[k]);
+    uint32_t d = digit(item[k]);
     dg[k] = d;
     uint64_t match = digit_match<DB>(d, valid);
     uint32_t before = (uint32_t)__popcll(match & lt);
@@ -1839,18 +1823,17 @@ k_rsort_scatter(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uin
     if (wbase + (uint32_t)k * 64 < tile_n) {
       uint32_t d = dg[k];
       stage[tstart[d] + whist[w][d] + rk[k]] = item[k];
-      if (BINS) stage_d[tstart[d] + whist[w][d] + rk[k]] = (uint16_t)d;
     }
   }
   block_sync();
   for (uint32_t j = t; j < tile_n; j += RS_THREADS) {
     uint64_t it = stage[j];
-    uint32_t d = BINS ? (uint32_t)stage_d[j] : digit(it);
+    uint32_t d = digit(it);
     out[(uint64_t)goff[d] + (j - tstart[d])] = it;
   }
 }
 
-// Tile-major bin counts (counts[tile * 512 + bin], written by k_edge_pass_tiles<..., TM>) ->
+// Tile-major bin counts (counts[tile * 512 + bin], written by k_edge_pass_tiles) ->
 // tile-major global offsets, in three coalesced passes over groups of TM_G tiles:
 //   k_tm_colsum       gsum[g][bin] = records of the bin in group g;
 //   k_tm_scan_groups  gsum[g][bin] <- exclusive prefix over groups; bin_start = exclusive
@@ -1997,9 +1980,12 @@ k_bin_scatter(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint6
   }
 }
 
-void bin_sort_u64(const uint64_t* in, uint64_t* out, uint64_t n, const uint32_t* bins, uint32_t nb,
-                  uint32_t* tmp, unsigned long long* bin_start, const uint16_t* digits,
-                  hipStream_t s, unsigned long long* h_start, hipEvent_t started) {
+// The scatter by bin: tmp holds launch_edge_pass_bins's tile counts (rsort_layout(n)), digits
+// each item's bin; bin_start: nb + 1 u64; h_start (pinned, nullable): bin_start copied out before
+// the scatter, `started` recorded once it is written.
+static void bin_sort_u64(const uint64_t* in, uint64_t* out, uint64_t n, uint32_t nb, uint32_t* tmp,
+                         unsigned long long* bin_start, const uint16_t* digits, hipStream_t s,
+                         unsigned long long* h_start, hipEvent_t started) {
   // the bin starts are known before the scatter: the caller may read them while it runs
   auto publish = [&]() {
     if (h_start) {
@@ -2007,20 +1993,16 @@ void bin_sort_u64(const uint64_t* in, uint64_t* out, uint64_t n, const uint32_t*
       (void)hipEventRecord(started, s);
     }
   };
-  uint64_t nt = (n + RS_TILE - 1) / RS_TILE;
-  uint32_t* counts = tmp;
+  const RsortLayout L = rsort_layout(n);
+  uint32_t* counts = tmp + L.counts;
   if (n == 0) return;
-  tm_offsets(counts, counts, (uint32_t)nt, 512, nb, tmp + 512 * nt, bin_start, s);
+  tm_offsets(counts, counts, (uint32_t)L.ntiles, 512, nb, tmp + L.gsum, bin_start, s);
   publish();
   hipLaunchKernelGGL(k_bin_scatter, dim3((unsigned)((n + BS_TILE - 1) / BS_TILE)), dim3(1024), 0, s,
                      in, out, n, (const uint32_t*)counts, digits);
 }
 
-size_t rsort_tmp_words(uint64_t n) {
-  uint64_t nt = (n + RS_TILE - 1) / RS_TILE;
-  // counts; then the flat scan's tmp, or the group sums + 513 u64 column starts (tile-major)
-  return 512 * nt + std::max<size_t>(scan_tmp_words(512 * nt), 512 * ((nt + TM_G - 1) / TM_G) + 1030);
-}
+size_t rsort_tmp_words(uint64_t n) { return rsort_layout(n).total; }
 
 // Digit width of the first pass when `bits` are sorted in passes of <= 9 bits (even split,
 // wider first): 25 bits -> 9+8+8, 18 -> 9+9.
@@ -2035,11 +2017,10 @@ int rsort_first_width(int bits) {
 // counted0: the first pass's tile histograms are already in tmp (k_edge_pass_tiles).
 uint64_t* radix_sort_u64(const uint64_t* in, uint64_t* a, uint64_t* b, uint64_t n, int bit_lo,
                          int bit_hi, uint32_t* tmp, hipStream_t s, bool counted0) {
-  uint64_t nt = (n + RS_TILE - 1) / RS_TILE;
-  uint32_t* counts = tmp;
-  uint32_t* stmp = tmp + 512 * nt;
-  unsigned long long* dstart =
-      (unsigned long long*)(((uintptr_t)(stmp + 512 * ((nt + TM_G - 1) / TM_G)) + 7) & ~(uintptr_t)7);
+  const RsortLayout L = rsort_layout(n);
+  const uint64_t nt = L.ntiles;
+  uint32_t *counts = tmp + L.counts, *stmp = tmp + L.gsum;
+  unsigned long long* dstart = (unsigned long long*)(tmp + L.dstart);
   const uint64_t* src = in;
   uint64_t* dst = a;
   for (int shift = bit_lo, p = 0; shift < bit_hi; ++p) {
@@ -2048,19 +2029,13 @@ uint64_t* radix_sort_u64(const uint64_t* in, uint64_t* a, uint64_t* b, uint64_t 
       bool count = !(p == 0 && counted0);
       const dim3 g((unsigned)nt), bl(RS_THREADS);
       if (width > 8) {
-        if (count)
-          hipLaunchKernelGGL((k_rsort_count<9, true>), g, bl, 0, s, src, n, shift, counts, (uint32_t)nt);
+        if (count) hipLaunchKernelGGL(k_rsort_count<9>, g, bl, 0, s, src, n, shift, counts);
         tm_offsets(counts, counts, (uint32_t)nt, 512, 512, stmp, dstart, s);
-        hipLaunchKernelGGL((k_rsort_scatter<9, false, true>), g, bl,
-                           0, s, src, dst, n, shift, (const uint32_t*)counts, (uint32_t)nt,
-                           (const uint32_t*)nullptr, 0u, (const uint16_t*)nullptr);
+        hipLaunchKernelGGL(k_rsort_scatter<9>, g, bl, 0, s, src, dst, n, shift, (const uint32_t*)counts);
       } else {
-        if (count)
-          hipLaunchKernelGGL((k_rsort_count<8, true>), g, bl, 0, s, src, n, shift, counts, (uint32_t)nt);
+        if (count) hipLaunchKernelGGL(k_rsort_count<8>, g, bl, 0, s, src, n, shift, counts);
         tm_offsets(counts, counts, (uint32_t)nt, 256, 256, stmp, dstart, s);
-        hipLaunchKernelGGL((k_rsort_scatter<8, false, true>), g, bl,
-                           0, s, src, dst, n, shift, (const uint32_t*)counts, (uint32_t)nt,
-                           (const uint32_t*)nullptr, 0u, (const uint16_t*)nullptr);
+        hipLaunchKernelGGL(k_rsort_scatter<8>, g, bl, 0, s, src, dst, n, shift, (const uint32_t*)counts);
       }
     }
     shift += width;
@@ -2343,12 +2318,15 @@ void launch_chunk_degsum(const uint32_t* seq, const uint32_t* deg, uint32_t n_se
 // any (keep many gathers in flight).  pst (nullable): pst_weight[lo] += 1 per record (above).
 // PRE: the records are k_part's output (x, ry): rank[y] was gathered already (or is one of the
 // sentinels RY_SELF / RY_OUT), only rank[x] is gathered here.
-// TM: the tile histograms are written tile-major (bin_sort_u64's k_tm_* passes).
-template <int DB, bool PRE, bool BINS = false, bool TM = false>
+// BINS: the digit is the hi bin (bin_of over the nb bounds in bins), also written to digits.
+// The tile histograms are written tile-major (tm_offsets).
+// plain (1 exactly where BINS): count by plain LDS atomics, no ballot match.  It stays a run-time
+// argument: as a compile-time test the BINS kernels take 46 / 52 VGPRs instead of 34.
+template <int DB, bool PRE, bool BINS = false>
 __global__ void __launch_bounds__(RS_THREADS)
 k_edge_pass_tiles(const uint2* __restrict__ uv, uint64_t m, const uint32_t* __restrict__ rank,
                   uint32_t n_rank, uint32_t* __restrict__ pst, uint64_t* __restrict__ items,
-                  uint32_t* err, int shift, uint32_t* __restrict__ counts, uint32_t ntiles,
+                  uint32_t* err, int shift, uint32_t* __restrict__ counts,
                   const uint32_t* __restrict__ bins = nullptr, uint32_t nb = 0,
                   uint16_t* __restrict__ digits = nullptr, int plain = 0) {
   constexpr uint32_t NBIN = 1u << DB;
@@ -2408,34 +2386,35 @@ k_edge_pass_tiles(const uint2* __restrict__ uv, uint64_t m, const uint32_t* __re
     }
   }
   block_sync();
-  for (uint32_t i = t; i < NBIN; i += RS_THREADS)
-    counts[TM ? (uint64_t)blockIdx.x * NBIN + i : (uint64_t)i * ntiles + blockIdx.x] = hist[i];
+  for (uint32_t i = t; i < NBIN; i += RS_THREADS) counts[(uint64_t)blockIdx.x * NBIN + i] = hist[i];
+}
+
+// The edge pass counting hi bins (no pst; nb <= 512 bounds) into tmp (rsort_layout(m)'s counts:
+// every tile writes all 512 of its counts); digits: m u16, each item's bin for bin_sort_u64.
+// pre: uv holds k_part's (x, ry) records.
+static void launch_edge_pass_bins(const uint32_t* uv, uint64_t m, const uint32_t* rank,
+                                  uint32_t n_rank, uint64_t* items, uint32_t* err,
+                                  const uint32_t* bins, uint32_t nb, uint32_t* tmp,
+                                  uint16_t* digits, hipStream_t s, bool pre) {
+  if (m == 0) return;
+  const RsortLayout L = rsort_layout(m);
+  auto k = pre ? k_edge_pass_tiles<9, true, true> : k_edge_pass_tiles<9, false, true>;
+  hipLaunchKernelGGL(k, dim3((unsigned)L.ntiles), dim3(RS_THREADS), 0, s, (const uint2*)uv, m, rank,
+                     n_rank, (uint32_t*)nullptr, items, err, 0, tmp + L.counts, bins, nb, digits, 1);
 }
 
 // Edge pass whose output feeds radix_sort_u64(..., bit_lo = shift, counted0 = true): tmp is
 // that sort's tmp (rsort_tmp_words(m)); DB = rsort_first_width of the sorted bit range.
 // pre: uv holds k_part's (x, ry) records.
-void launch_edge_pass_bins(const uint32_t* uv, uint64_t m, const uint32_t* rank, uint32_t n_rank,
-                           uint64_t* items, uint32_t* err, const uint32_t* bins, uint32_t nb,
-                           uint32_t* tmp, uint16_t* digits, hipStream_t s, bool pre) {
-  if (m == 0) return;
-  uint64_t nt = (m + RS_TILE - 1) / RS_TILE;
-  // tile-major counts (every tile writes all 512 of its counts); bin counts by plain LDS atomics
-  auto k = pre ? k_edge_pass_tiles<9, true, true, true> : k_edge_pass_tiles<9, false, true, true>;
-  hipLaunchKernelGGL(k, dim3((unsigned)nt), dim3(RS_THREADS), 0, s, (const uint2*)uv, m, rank, n_rank,
-                     (uint32_t*)nullptr, items, err, 0, tmp, (uint32_t)nt, bins, nb, digits, 1);
-}
-
 void launch_edge_pass_tiles(const uint32_t* uv, uint64_t m, const uint32_t* rank, uint32_t n_rank,
                             uint32_t* pst, uint64_t* items, uint32_t* err, int shift, int DB,
                             uint32_t* tmp, hipStream_t s, bool pre) {
   if (m == 0) return;
-  uint64_t nt = (m + RS_TILE - 1) / RS_TILE;
-  // tile-major counts: the layout radix_sort_u64(..., counted0) expects
-  auto k = DB > 8 ? (pre ? k_edge_pass_tiles<9, true, false, true> : k_edge_pass_tiles<9, false, false, true>)
-                  : (pre ? k_edge_pass_tiles<8, true, false, true> : k_edge_pass_tiles<8, false, false, true>);
-  hipLaunchKernelGGL(k, dim3((unsigned)nt), dim3(RS_THREADS), 0, s, (const uint2*)uv, m, rank, n_rank,
-                     pst, items, err, shift, tmp, (uint32_t)nt, (const uint32_t*)nullptr, 0u,
+  const RsortLayout L = rsort_layout(m);
+  auto k = DB > 8 ? (pre ? k_edge_pass_tiles<9, true> : k_edge_pass_tiles<9, false>)
+                  : (pre ? k_edge_pass_tiles<8, true> : k_edge_pass_tiles<8, false>);
+  hipLaunchKernelGGL(k, dim3((unsigned)L.ntiles), dim3(RS_THREADS), 0, s, (const uint2*)uv, m, rank,
+                     n_rank, pst, items, err, shift, tmp + L.counts, (const uint32_t*)nullptr, 0u,
                      (uint16_t*)nullptr, 0);
 }
 
@@ -2445,7 +2424,7 @@ uint64_t* group_by_bins(const uint32_t* uv, bool pre, uint64_t m, const uint32_t
                         unsigned long long* bin_start, hipStream_t s,
                         unsigned long long* h_start, hipEvent_t started) {
   launch_edge_pass_bins(uv, m, rank, n_rank, items, err, bins, nb, tmp, digits, s, pre);
-  bin_sort_u64(items, items_b, m, bins, nb, tmp, bin_start, digits, s, h_start, started);
+  bin_sort_u64(items, items_b, m, nb, tmp, bin_start, digits, s, h_start, started);
   return items_b;
 }
 
@@ -3178,14 +3157,11 @@ void launch_part_gather(const uint32_t* uv, uint64_t m, const uint32_t* rank, ui
 // edge — the same unique result as Liu's sequential union-find (jtree.cpp:73-83,
 // unionfind.h:46-102), independent of insertion order and interleaving.
 // ---------------------------------------------------------------------------------------
-// Parent loads.  LOAD 0: relaxed agent-scope atomic load (global_load sc1: bypasses L1, L2
-// served); 1: relaxed system-scope; 2: a returning atomic OR 0 (performed at memory, always
-// fresh).  Staleness never breaks correctness (see above), only costs extra CAS round trips.
-template <int LOAD>
+// Parent loads: relaxed agent-scope atomic loads (global_load sc1: bypasses L1, L2 served).
+// Staleness never breaks correctness (see above), only costs extra CAS round trips.  (System-scope
+// loads and a returning atomic OR 0, performed at memory and always fresh, were the alternatives.)
 __device__ __forceinline__ uint32_t ld_parent(uint32_t* p) {
-  if (LOAD == 0) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (LOAD == 1) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  return atomicOr(p, 0u);
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 struct ZState {
@@ -3214,7 +3190,7 @@ struct ZRec {  // where to record pre-bucket roots (x < B0) that a CAS links for
   uint32_t B0 = 0;
   uint32_t* linked = nullptr;
   uint32_t* n_linked = nullptr;
-  // block-local staging (LDS, nullable): appends reserve here with LDS atomics and the block
+  // block-local staging (LDS): appends reserve here with LDS atomics and the block
   // flushes once at its end (zip_flush_linked) — one global counter hit by every wave at
   // every step serialises (~88 returning atomics per microsecond on one word)
   uint32_t* lbuf = nullptr;
@@ -3235,8 +3211,11 @@ struct ZRec {  // where to record pre-bucket roots (x < B0) that a CAS links for
 //     (x, b) and (y, b) give the same threshold connectivity).
 struct SpineInfo {
   const uint32_t* bitmap = nullptr;
-  uint32_t B0 = 0, B1 = 0, G = INV, limit = 64;
+  uint32_t B0 = 0, B1 = 0, G = INV;
 };
+constexpr uint32_t KB_SCAN_LIMIT = 64;  // spine scans (sp_pred, k_kb_spine): bitmap words per search
+// The stride of the kb loop's parent[]: interleaved with the hints (ld_pj below, k_pj_init).
+constexpr uint32_t KB_PS = 2;
 
 __device__ __forceinline__ bool sp_marked(const SpineInfo& sp, uint32_t v) {
   return v >= sp.B0 && v < sp.B1 && ((sp.bitmap[v >> 5] >> (v & 31)) & 1u);
@@ -3251,12 +3230,12 @@ __device__ __forceinline__ uint32_t word_in(const uint32_t* bitmap, uint32_t w, 
   return bits;
 }
 
-// Highest marked y with x < y < b (scans at most sp.limit words below b's); INV if none.
+// Highest marked y with x < y < b (scans at most KB_SCAN_LIMIT words below b's); INV if none.
 __device__ __forceinline__ uint32_t sp_pred(const SpineInfo& sp, uint32_t b, uint32_t x) {
   uint32_t lo = max(x + 1, sp.B0);
   if (b <= lo) return INV;
   uint32_t w = (b - 1) >> 5, wl = lo >> 5;
-  for (uint32_t k = 0; k <= sp.limit; ++k) {
+  for (uint32_t k = 0; k <= KB_SCAN_LIMIT; ++k) {
     uint32_t bits = word_in(sp.bitmap, w, lo, b);
     if (bits) return (w << 5) + 31 - __clz(bits);
     if (w == wl) break;
@@ -3270,7 +3249,7 @@ __device__ __forceinline__ uint32_t sp_pred(const SpineInfo& sp, uint32_t b, uin
 // one 8-byte relaxed agent-scope load — one cache line per step, not two.  (The hint half is
 // written with plain stores and the parent half only by CAS: write-back L2s merge dirty bytes
 // only, so neither half overwrites the other.)
-template <int LOAD, int S>
+template <int S>
 __device__ __forceinline__ void ld_pj(uint32_t* parent, uint32_t* jump, uint32_t x, uint32_t& p,
                                       uint32_t& j) {
   if (S == 2) {
@@ -3279,16 +3258,16 @@ __device__ __forceinline__ void ld_pj(uint32_t* parent, uint32_t* jump, uint32_t
     p = (uint32_t)w;
     j = (uint32_t)(w >> 32);
   } else {
-    p = ld_parent<LOAD>(&parent[x]);
+    p = ld_parent(&parent[x]);
     j = jump ? jump[x] : 0u;
   }
 }
 
-template <int LOAD, int JUMP, bool STATS, bool REC = false, bool SPINE = false, int S = 1>
+// jump: the hint array (S = 1 only; S = 2 takes the hints from parent + 1).
+template <bool STATS, bool REC = false, bool SPINE = false, int S = 1>
 __device__ __forceinline__ bool zip_step(uint32_t* parent, uint32_t* jump, ZState& s, ZCount& c,
                                          const ZRec& rec = ZRec(),
                                          const SpineInfo& sp = SpineInfo()) {
-  static_assert(S == 1 || JUMP, "interleaved parent / hint");
   uint32_t* const jp = S == 2 ? parent + 1 : jump;  // jp[S * v]: the hint of v
   if (STATS) c.steps++;
   if (!s.fresh) {
@@ -3298,7 +3277,7 @@ __device__ __forceinline__ bool zip_step(uint32_t* parent, uint32_t* jump, ZStat
     const bool chk = SPINE && !(s.flags & ZF_SPINE);
     const uint32_t mw = (chk && s.x >= sp.B0 && s.x < sp.B1) ? sp.bitmap[s.x >> 5] : 0u;
     uint32_t pj, j;
-    ld_pj<LOAD, S>(parent, JUMP ? jump : nullptr, s.x, pj, j);
+    ld_pj<S>(parent, jump, s.x, pj, j);
     if (chk && (s.x == sp.G || ((mw >> (s.x & 31)) & 1u))) {
       s.flags |= ZF_SPINE;
       if (!(s.flags & ZF_KEEP) && sp_marked(sp, s.b)) return true;
@@ -3306,16 +3285,14 @@ __device__ __forceinline__ bool zip_step(uint32_t* parent, uint32_t* jump, ZStat
       if (y != INV) {
         s.prev = INV;
         s.x = y;
-        ld_pj<LOAD, S>(parent, JUMP ? jump : nullptr, s.x, pj, j);
+        ld_pj<S>(parent, jump, s.x, pj, j);
       }
     }
-    if (JUMP) {
-      if (j > s.x && j < s.b) {
-        if (s.prev != INV) jp[(size_t)S * s.prev] = j;
-        s.prev = s.x;
-        s.x = j;
-        return false;
-      }
+    if (j > s.x && j < s.b) {
+      if (s.prev != INV) jp[(size_t)S * s.prev] = j;
+      s.prev = s.x;
+      s.x = j;
+      return false;
     }
     s.p = pj;
   }
@@ -3325,12 +3302,12 @@ __device__ __forceinline__ bool zip_step(uint32_t* parent, uint32_t* jump, ZStat
       raise_fault(FAULT_FOREST);
       return true;
     }
-    if (JUMP && s.prev != INV) jp[(size_t)S * s.prev] = s.p;
+    if (s.prev != INV) jp[(size_t)S * s.prev] = s.p;
     s.prev = s.x;
     s.x = s.p;
     return false;
   }
-  if (JUMP && s.x != s.a) jp[(size_t)S * s.a] = s.x;
+  if (s.x != s.a) jp[(size_t)S * s.a] = s.x;
   if (s.p == s.b) return true;
   if (STATS) c.cas++;
   uint32_t old = atomicCAS(&parent[(size_t)S * s.x], s.p, s.b);
@@ -3397,12 +3374,15 @@ struct EdgeSrc {
 
 // Queue chunk (edges per wave refill): all waves sweep the list together, so about
 // nwaves * chunk edges are in flight — the concurrency window that the zipper's rework grows
-// with.  Set per launch by the host (qchunk).
-template <int LOAD, int JUMP, bool STATS, bool REC, bool SPINE = false, int S = 1>
-__device__ __forceinline__ void tree_queue_body(EdgeSrc src, uint64_t n,
-                                                uint32_t* parent, uint32_t* jump,
-                                                unsigned long long* stats,
-                                                const ZRec& rec, uint32_t CH = 512,
+// with (tree phase, RMAT-26: 26.3 / 25.6 / 25.3 / 25.8 ms at 64 / 256 / 512 / 1024;
+// twitter-shape: 37.7 / 37.6 / 38.9 ms at 64 / 256 / 512; LJ-shape within noise).
+constexpr uint32_t KB_QCHUNK = 256;
+
+// pj: the kb loop's interleaved parents and hints (ld_pj, S = 2).  With REC, rec.lbuf is the
+// block's LDS buffer.
+template <bool STATS, bool REC, bool SPINE>
+__device__ __forceinline__ void tree_queue_body(EdgeSrc src, uint64_t n, uint32_t* pj,
+                                                unsigned long long* stats, const ZRec& rec,
                                                 const SpineInfo& sp = SpineInfo()) {
   const int lane = threadIdx.x & 63;
   const uint64_t lt = lane ? (~0ull >> (64 - lane)) : 0ull;
@@ -3422,11 +3402,11 @@ __device__ __forceinline__ void tree_queue_body(EdgeSrc src, uint64_t n,
         // the wave's next chunk: static stride over the grid, so all waves sweep the edge
         // list together in increasing order with no shared counter (a single global cursor
         // serialises: one same-address atomic per chunk)
-        uint64_t st = (wave_id + chunk_k * nwaves) * (uint64_t)CH;
+        uint64_t st = (wave_id + chunk_k * nwaves) * (uint64_t)KB_QCHUNK;
         ++chunk_k;
         if (st >= n) { exhausted = true; break; }
         cbase = st;
-        cend = st + CH < n ? st + CH : n;
+        cend = st + KB_QCHUNK < n ? st + KB_QCHUNK : n;
       }
       uint32_t k = (uint32_t)__popcll(freem & lt);
       uint64_t cnt = (uint64_t)__popcll(freem);
@@ -3446,7 +3426,7 @@ __device__ __forceinline__ void tree_queue_body(EdgeSrc src, uint64_t n,
     }
     if (__ballot(active) == 0) break;
     bool linked = false;
-    if (active && zip_step<LOAD, JUMP, STATS, REC, SPINE, S>(parent, jump, s, c, rec, sp)) {
+    if (active && zip_step<STATS, REC, SPINE, 2>(pj, nullptr, s, c, rec, sp)) {
       active = false;
       linked = REC && (s.flags & ZF_LINKED);
       if (STATS) { maxsteps = max(maxsteps, c.steps - st0); c.one += c.steps - st0 == 1; }
@@ -3456,25 +3436,19 @@ __device__ __forceinline__ void tree_queue_body(EdgeSrc src, uint64_t n,
       if (bal) {
         const int leader = __ffsll((unsigned long long)bal) - 1;
         const uint32_t cnt = (uint32_t)__popcll(bal), r = (uint32_t)__popcll(bal & lt);
-        if (rec.lbuf) {  // the block's LDS buffer; what does not fit goes straight out
-          uint32_t base = 0;
-          if (lane == leader) base = atomicAdd(rec.lcnt, cnt);
-          base = __builtin_amdgcn_readlane(base, leader);
-          const uint32_t over0 = base > rec.lcap ? base : rec.lcap;
-          const uint32_t nover = base + cnt > over0 ? base + cnt - over0 : 0u;
-          uint32_t g = 0;
-          if (nover && lane == leader) g = atomicAdd(rec.n_linked, nover);
-          g = __builtin_amdgcn_readlane(g, leader);
-          if (linked) {
-            const uint32_t slot = base + r;
-            if (slot < rec.lcap) rec.lbuf[slot] = s.x;
-            else rec.linked[g + (slot - over0)] = s.x;
-          }
-        } else {
-          uint32_t base = 0;
-          if (lane == leader) base = atomicAdd(rec.n_linked, cnt);
-          base = __builtin_amdgcn_readlane(base, leader);
-          if (linked) rec.linked[base + r] = s.x;
+        // into the block's LDS buffer; what does not fit goes straight out
+        uint32_t base = 0;
+        if (lane == leader) base = atomicAdd(rec.lcnt, cnt);
+        base = __builtin_amdgcn_readlane(base, leader);
+        const uint32_t over0 = base > rec.lcap ? base : rec.lcap;
+        const uint32_t nover = base + cnt > over0 ? base + cnt - over0 : 0u;
+        uint32_t g = 0;
+        if (nover && lane == leader) g = atomicAdd(rec.n_linked, nover);
+        g = __builtin_amdgcn_readlane(g, leader);
+        if (linked) {
+          const uint32_t slot = base + r;
+          if (slot < rec.lcap) rec.lbuf[slot] = s.x;
+          else rec.linked[g + (slot - over0)] = s.x;
         }
       }
     }
@@ -3486,7 +3460,7 @@ __device__ void zip_insert(uint32_t* parent, uint32_t* jump, uint32_t a, uint32_
   ZState s;
   ZCount c;
   zstart(s, a, b);
-  while (!zip_step<0, 1, false>(parent, jump, s, c)) {
+  while (!zip_step<false>(parent, jump, s, c)) {
   }
 }
 
@@ -4055,7 +4029,7 @@ k_kb_pick(const uint32_t* uf, uint32_t B0lim, const uint32_t* __restrict__ anc_p
 // connect G with exactly the marked ranks present.  The path edges (b_i, b_i+1) are written
 // straight into the forest (parent[] of every in-bucket rank is still INVALID here, so this
 // is what the zipper would do, in one store).  A run of marks is cut where the next mark is
-// more than `limit` words away; each run's first mark b is queued as the edge (G, b), which
+// more than KB_SCAN_LIMIT words away; each run's first mark b is queued as the edge (G, b), which
 // the zipper inserts (walking G's chain).  One thread per bitmap word; the forward search of
 // a word's last mark and the backward search of a word's first mark are symmetric, so every
 // mark gets exactly one incoming connection.
@@ -4069,13 +4043,11 @@ k_kb_pick(const uint32_t* uf, uint32_t B0lim, const uint32_t* __restrict__ anc_p
 // (see k_kb_map).
 // Split lockstep (P ranks, launch_ls_apply_split): CHAIN writes only the forest part (parent,
 // spq: the bucket's zipper owner), FOLD only the union-find part (uf, gbits: every rank).
-// ps: the stride of parent[] (2: interleaved with the hints, see ld_pj).
 template <bool CHAIN, bool FOLD>
 __global__ void k_kb_spine(const uint32_t* __restrict__ bitmap, uint32_t B0, uint32_t B1,
-                           uint32_t* parent, uint32_t* spq, uint32_t* n_spine, uint32_t limit,
-                           uint32_t* uf, uint32_t anchor, uint32_t* gbits,
-                           const uint32_t* __restrict__ gx, const uint32_t* __restrict__ anc,
-                           uint32_t ps) {
+                           uint32_t* parent, uint32_t* spq, uint32_t* n_spine, uint32_t* uf,
+                           uint32_t anchor, uint32_t* gbits, const uint32_t* __restrict__ gx,
+                           const uint32_t* __restrict__ anc) {
   const uint32_t w0 = B0 >> 5, w1 = (B1 - 1) >> 5;
   const uint32_t R = FOLD ? uf_find_ro(uf, anchor_rank(anchor, anc)) : INV;
   const uint32_t X = (FOLD && gbits) ? *gx : INV;
@@ -4096,17 +4068,17 @@ __global__ void k_kb_spine(const uint32_t* __restrict__ bitmap, uint32_t B0, uin
     while (bits) {
       uint32_t nx = (w << 5) + __ffs(bits) - 1;
       bits &= bits - 1;
-      if (CHAIN) parent[(size_t)ps * cur] = nx;
+      if (CHAIN) parent[(size_t)KB_PS * cur] = nx;
       if (FOLD) uf[nx] = R;
       cur = nx;
     }
     if (!CHAIN) continue;
-    for (uint32_t v = w + 1, k = 0; v <= w1 && k < limit; ++v, ++k) {
+    for (uint32_t v = w + 1, k = 0; v <= w1 && k < KB_SCAN_LIMIT; ++v, ++k) {
       uint32_t nb = word_in(bitmap, v, B0, B1);
-      if (nb) { parent[(size_t)ps * cur] = (v << 5) + __ffs(nb) - 1; break; }
+      if (nb) { parent[(size_t)KB_PS * cur] = (v << 5) + __ffs(nb) - 1; break; }
     }
     bool has_pred = false;
-    for (uint32_t v = w, k = 0; v > w0 && k < limit; --v, ++k)
+    for (uint32_t v = w, k = 0; v > w0 && k < KB_SCAN_LIMIT; --v, ++k)
       if (word_in(bitmap, v - 1, B0, B1)) { has_pred = true; break; }
     if (!has_pred) spq[atomicAdd(n_spine, 1u)] = first;
   }
@@ -4123,7 +4095,7 @@ __global__ void k_kb_spine(const uint32_t* __restrict__ bitmap, uint32_t B0, uin
 // run (every chain of the bucket in flight at once, against the current union-find), and a
 // miss that reaches the giant sets its bit in gbits (nullable) when the bitmap's reference
 // vertex *gx lies in the anchor's component.
-// drop2: an in-bucket pair (a, b), B0 <= a < b, whose two ranks are both marked is dropped too:
+// An in-bucket pair (a, b), B0 <= a < b, whose two ranks are both marked is dropped too:
 // both are ancestors of G through their own edges to G's component, so b is already an ancestor
 // of a without this edge (zip_step would stop it at its first step; here it costs two bitmap
 // reads in a flat stream instead of a lane of the zipper's queue).  A mark this launch has not
@@ -4144,7 +4116,7 @@ __global__ void k_kb_refresh(uint64_t* kept, const uint32_t* __restrict__ n_kept
                              uint32_t* uf, const uint32_t* __restrict__ label, uint32_t* bitmap,
                              uint32_t B0, uint32_t anchor, uint32_t* gbits,
                              const uint32_t* __restrict__ gx, const uint32_t* __restrict__ anc,
-                             int drop2, uint32_t* pj = nullptr) {
+                             uint32_t* pj = nullptr) {
   const uint32_t nk = *n_kept;
   anchor = anchor_rank(anchor, anc);
   const uint32_t RG = anchor != INV ? uf_find_ro(uf, anchor) : INV;
@@ -4154,7 +4126,7 @@ __global__ void k_kb_refresh(uint64_t* kept, const uint32_t* __restrict__ n_kept
     const uint64_t it = kept[i];
     const uint32_t g = (uint32_t)it, b = (uint32_t)(it >> 32);
     if (g >= B0) {
-      if (drop2 && RG != INV && b != INV && ((bitmap[g >> 5] >> (g & 31)) & 1u) &&
+      if (RG != INV && b != INV && ((bitmap[g >> 5] >> (g & 31)) & 1u) &&
           ((bitmap[b >> 5] >> (b & 31)) & 1u))
         kept[i] = ~0ull;
       continue;
@@ -4186,14 +4158,13 @@ __global__ void k_kb_refresh(uint64_t* kept, const uint32_t* __restrict__ n_kept
 // REC = false (split lockstep, the bucket's zipper owner): no linked roots are recorded (every
 // rank unions the pairs themselves), and G comes from *gslot, captured before the bucket's
 // union-find changed (anchor != INV means there is one).
-template <bool STATS, bool REC = true, int S = 2>
+template <bool STATS, bool REC = true>
 __global__ void k_kb_zip(const uint64_t* __restrict__ kept, const uint32_t* __restrict__ n_kept,
                          const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ spq,
                          const uint32_t* __restrict__ n_spine, uint32_t B0, uint32_t B1,
-                         uint32_t* uf, const uint32_t* __restrict__ label, uint32_t* parent,
-                         uint32_t* jump, unsigned long long* stats, uint32_t* linked,
-                         uint32_t* n_linked, uint32_t anchor, uint32_t scan_limit,
-                         uint32_t qchunk, const uint32_t* __restrict__ anc,
+                         uint32_t* uf, const uint32_t* __restrict__ label, uint32_t* pj,
+                         unsigned long long* stats, uint32_t* linked, uint32_t* n_linked,
+                         uint32_t anchor, const uint32_t* __restrict__ anc,
                          const uint32_t* __restrict__ gslot = nullptr) {
   constexpr uint32_t LCAP = REC ? 2048 : 1;
   __shared__ uint32_t lbuf[LCAP];
@@ -4218,13 +4189,12 @@ __global__ void k_kb_zip(const uint64_t* __restrict__ kept, const uint32_t* __re
     sp.B0 = B0;
     sp.B1 = B1;
     sp.G = gslot ? *gslot : label[uf_find_ro(uf, anchor)];
-    sp.limit = scan_limit;
     src.spq = spq;
     src.G = sp.G;
     src.np = *n_spine;
-    tree_queue_body<0, 1, STATS, REC, true, S>(src, src.np + nk, parent, jump, stats, rec, qchunk, sp);
+    tree_queue_body<STATS, REC, true>(src, src.np + nk, pj, stats, rec, sp);
   } else {
-    tree_queue_body<0, 1, STATS, REC, false, S>(src, nk, parent, jump, stats, rec, qchunk);
+    tree_queue_body<STATS, REC, false>(src, nk, pj, stats, rec);
   }
   if (!REC) return;
   // the block's staged linked roots: one reservation, a coalesced copy
@@ -4242,10 +4212,12 @@ __global__ void k_kb_zip(const uint64_t* __restrict__ kept, const uint32_t* __re
 // FOLD: the giant fold ran (k_kb_spine); links between two marked ranks are skipped, and the marks are cleared
 // by k_kb_label instead (this launch reads them).
 // linked / n_linked: the pre-bucket roots the zipper linked (k_kb_zip, REC).
+// parent: the kb loop's, here and in k_kb_label (stride KB_PS; this kernel takes it as the
+// argument ps, see profiles/sort_tree_modes/README.md).
 template <bool FOLD>
 __global__ void k_kb_union(const uint32_t* __restrict__ parent, uint32_t* uf, uint32_t B0,
-                           uint32_t B1, uint32_t* bitmap,
-                           uint32_t anchor, const uint32_t* __restrict__ anc, uint32_t ps,
+                           uint32_t B1, uint32_t* bitmap, uint32_t anchor,
+                           const uint32_t* __restrict__ anc, uint32_t ps,
                            const uint32_t* __restrict__ linked,
                            const uint32_t* __restrict__ n_linked,
                            const uint64_t* __restrict__ kept = nullptr,
@@ -4286,12 +4258,11 @@ __global__ void k_kb_union(const uint32_t* __restrict__ parent, uint32_t* uf, ui
 // reference vertex *gx gets its bit (one ballot-assembled word per 32 ranks).
 __global__ void k_kb_label(const uint32_t* __restrict__ parent, uint32_t* uf, uint32_t* label,
                            uint32_t B0, uint32_t B1, uint32_t* counters, uint32_t* bitmap,
-                           int clear_marks, uint32_t* gbits, const uint32_t* __restrict__ gx,
-                           uint32_t ps = 1) {
+                           int clear_marks, uint32_t* gbits, const uint32_t* __restrict__ gx) {
   const uint32_t X = gbits ? *gx : INV;
   if (X == INV) {
     for (uint32_t v = B0 + blockIdx.x * blockDim.x + threadIdx.x; v < B1; v += gridDim.x * blockDim.x)
-      if (parent[(size_t)ps * v] == INV) label[uf_find<false>(uf, v)] = v;
+      if (parent[(size_t)KB_PS * v] == INV) label[uf_find<false>(uf, v)] = v;
   } else {
     const uint32_t RX = uf_find_ro(uf, X);
     const uint32_t v0 = B0 & ~63u;  // waves cover whole 64-rank (two-word) groups
@@ -4301,7 +4272,7 @@ __global__ void k_kb_label(const uint32_t* __restrict__ parent, uint32_t* uf, ui
       bool in = false;
       if (v >= B0) {
         const uint32_t rt = uf_find<false>(uf, v);
-        if (parent[(size_t)ps * v] == INV) label[rt] = v;
+        if (parent[(size_t)KB_PS * v] == INV) label[rt] = v;
         in = rt == RX;
       }
       const uint64_t bal = __ballot(in);
@@ -4412,11 +4383,8 @@ void launch_kb_rebase(const KbState& S, size_t j, uint32_t B0lim, hipStream_t s)
 static bool kb_refresh_links() { return knobs().kb_rlink != 0; }
 
 void launch_kb_apply(const KbState& S, size_t k, uint32_t B0, uint32_t B1, uint32_t anchor,
-                     bool nonempty, uint64_t* kept, bool refresh, bool stats, size_t gx_slot,
-                     hipStream_t s) {
-  const uint32_t ps = 2;  // parent[2v], hint[2v + 1] (k_pj_init)
-  const uint32_t scan_limit = 64;  // spine scan: bitmap words per search
-  uint32_t *uf = S.uf, *label = S.label, *parent = S.parent(), *jump = S.jump();
+                     bool nonempty, uint64_t* kept, bool stats, size_t gx_slot, hipStream_t s) {
+  uint32_t *uf = S.uf, *label = S.label, *parent = S.parent();
   uint32_t *linked = S.linked, *bitmap = S.bm_of(k), *spq = S.spq_of(k), *gbits = S.gbits;
   uint32_t* counters = S.cnt_of(k);
   uint32_t* n_linked = counters + 1;
@@ -4428,28 +4396,23 @@ void launch_kb_apply(const KbState& S, size_t k, uint32_t B0, uint32_t B1, uint3
   // the map running beside it sees the giant's root unchanged
   const uint32_t *anc = S.anc_of(k), *anc_next = S.anc_of(k + 1);
   if (nonempty) {
-    if (refresh)
-      hipLaunchKernelGGL(k_kb_refresh, dim3(2048), dim3(BLOCK), 0, s, kept, (const uint32_t*)n_kept,
-                         uf, (const uint32_t*)label, bitmap, B0, anchor, gbits, gx, anc,
-                         1, kb_refresh_links() ? parent : (uint32_t*)nullptr);
+    hipLaunchKernelGGL(k_kb_refresh, dim3(2048), dim3(BLOCK), 0, s, kept, (const uint32_t*)n_kept,
+                       uf, (const uint32_t*)label, bitmap, B0, anchor, gbits, gx, anc,
+                       kb_refresh_links() ? parent : (uint32_t*)nullptr);
     if (anchor != INV)  // the spine, and the giant fold of the marked ranks
       hipLaunchKernelGGL((k_kb_spine<true, true>), dim3(grid_for(((uint64_t)(B1 - B0) + 31) / 32 + 1)), dim3(BLOCK),
-                         0, s, (const uint32_t*)bitmap, B0, B1, parent, spq, n_spine, scan_limit,
-                         uf, anchor, gbits, gx, anc, (uint32_t)ps);
+                         0, s, (const uint32_t*)bitmap, B0, B1, parent, spq, n_spine, uf, anchor,
+                         gbits, gx, anc);
     // the zipper records the pre-bucket roots it links (LDS staging, one reservation per block)
     // for k_kb_union.  (Reading them back as the kept pairs' starts instead, with no recording:
     // tree phase +0.7 ms RMAT-26, +0.8 ms LJ-shape, +1.7 ms twitter-shape — DESIGN.md §9.)
-    auto zk = stats ? k_kb_zip<true, true, 2> : k_kb_zip<false, true, 2>;
-    // zipper queue: edges per wave refill (tree phase, RMAT-26: 26.3 / 25.6 / 25.3 / 25.8 ms at
-    // 64 / 256 / 512 / 1024; twitter-shape: 37.7 / 37.6 / 38.9 ms at 64 / 256 / 512; LJ-shape
-    // within noise)
-    const uint32_t qchunk = 256;
+    auto zk = stats ? k_kb_zip<true, true> : k_kb_zip<false, true>;
     // (a narrower window — 256 or 64 blocks sweeping the pairs in increasing order — made the
     // percolation bucket's walks longer, not shorter: LJ tree 3.19 -> 3.65 / 6.21 ms)
     hipLaunchKernelGGL(zk, dim3(MAX_GRID), dim3(BLOCK), 0, s, kept, (const uint32_t*)n_kept,
                        (const uint32_t*)bitmap, (const uint32_t*)spq, (const uint32_t*)n_spine, B0,
-                       B1, uf, (const uint32_t*)label, parent, jump, st + 8, linked, n_linked,
-                       anchor, scan_limit, qchunk, anc, (const uint32_t*)nullptr);
+                       B1, uf, (const uint32_t*)label, parent, st + 8, linked, n_linked, anchor,
+                       anc, (const uint32_t*)nullptr);
   }
   // giant fold: the marks are relative to the anchor's component; its root R_a may later be
   // linked below the union's R (pipelined: different anchors) — the folded ranks follow it
@@ -4458,14 +4421,14 @@ void launch_kb_apply(const KbState& S, size_t k, uint32_t B0, uint32_t B1, uint3
   // over (hub buckets: ~500 ranks, ~0.3 M linked roots): a full grid, whatever the width
   unsigned ug = MAX_GRID;
   auto uk = fold ? k_kb_union<true> : k_kb_union<false>;
-  const bool rl = nonempty && refresh && kb_refresh_links();
+  const bool rl = nonempty && kb_refresh_links();
   hipLaunchKernelGGL(uk, dim3(ug), dim3(BLOCK), 0, s, (const uint32_t*)parent, uf, B0, B1,
-                     bitmap, B0 > 0 ? B0 - 1 : INV, anc_next, ps, (const uint32_t*)linked,
+                     bitmap, B0 > 0 ? B0 - 1 : INV, anc_next, KB_PS, (const uint32_t*)linked,
                      (const uint32_t*)n_linked, rl ? (const uint64_t*)kept : (const uint64_t*)nullptr,
                      rl ? (const uint32_t*)n_kept : (const uint32_t*)nullptr);
   hipLaunchKernelGGL(k_kb_label, dim3(grid_for((uint64_t)(B1 - B0) + 64)), dim3(BLOCK), 0, s,
                      (const uint32_t*)parent, uf, label, B0, B1, counters, bitmap, (int)fold,
-                     gbits, gx, ps);
+                     gbits, gx);
 }
 
 void launch_kb_refresh(const KbState& S, size_t k, uint64_t* kept, const uint32_t* n_kept,
@@ -4473,7 +4436,7 @@ void launch_kb_refresh(const KbState& S, size_t k, uint64_t* kept, const uint32_
                        hipStream_t s) {
   hipLaunchKernelGGL(k_kb_refresh, dim3(2048), dim3(BLOCK), 0, s, kept, n_kept, S.uf,
                      (const uint32_t*)S.label, bitmap, B0, anchor, S.gbits,
-                     (const uint32_t*)S.gx_of(gx_slot), (const uint32_t*)S.anc_of(k), 1);
+                     (const uint32_t*)S.gx_of(gx_slot), (const uint32_t*)S.anc_of(k));
 }
 
 // ---- split lockstep apply (P ranks; sheep_capi.cpp ls_apply) ------------------------------
@@ -4571,7 +4534,7 @@ void launch_ls_fold_union_label(const KbState& S, size_t k, uint32_t B0, uint32_
     if (anchor != INV && B1 > B0)  // the marked ranks go under the anchor's root (no forest)
       hipLaunchKernelGGL((k_kb_spine<false, true>), dim3(grid_for(((uint64_t)(B1 - B0) + 31) / 32 + 1)),
                          dim3(BLOCK), 0, s, (const uint32_t*)bitmap, B0, B1, nullptr, nullptr,
-                         nullptr, 0u, uf, anchor, gbits, gx, anc, 1u);
+                         nullptr, uf, anchor, gbits, gx, anc);
     if (cap)
       hipLaunchKernelGGL(k_ls_union_pairs, dim3(MAX_GRID), dim3(BLOCK), 0, s, recv, P, ms, cap, uf,
                          anchor_next, anc_next);
@@ -4588,19 +4551,16 @@ void launch_ls_fold_union_label(const KbState& S, size_t k, uint32_t B0, uint32_
 // pairs (zn[0] of them) and of the bucket's mark words; zn[1] = spine queue length (zeroed
 // here), zn[2] = G (launch_ls_gslot; INV: no giant).
 void launch_ls_zip(const uint64_t* zkept, uint32_t* zn, const uint32_t* zbm, uint32_t* zspq,
-                   uint32_t B0, uint32_t B1, bool has_anchor, uint32_t* parent, uint32_t* jump,
-                   hipStream_t s) {
-  const uint32_t ps = 2;
+                   uint32_t B0, uint32_t B1, bool has_anchor, uint32_t* parent, hipStream_t s) {
   (void)hipMemsetAsync(zn + 1, 0, 4, s);
   if (has_anchor && B1 > B0)
     hipLaunchKernelGGL((k_kb_spine<true, false>), dim3(grid_for(((uint64_t)(B1 - B0) + 31) / 32 + 1)),
-                       dim3(BLOCK), 0, s, zbm, B0, B1, parent, zspq, zn + 1, 64u, nullptr, 0u,
-                       nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, ps);
-  hipLaunchKernelGGL((k_kb_zip<false, false, 2>), dim3(MAX_GRID), dim3(BLOCK), 0, s, zkept,
+                       dim3(BLOCK), 0, s, zbm, B0, B1, parent, zspq, zn + 1, nullptr, 0u, nullptr,
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+  hipLaunchKernelGGL((k_kb_zip<false, false>), dim3(MAX_GRID), dim3(BLOCK), 0, s, zkept,
                      (const uint32_t*)zn, zbm, (const uint32_t*)zspq, (const uint32_t*)(zn + 1), B0, B1,
-                     nullptr, (const uint32_t*)nullptr, parent, jump, nullptr, nullptr, nullptr,
-                     has_anchor ? 0u : INV, 64u, 256u, (const uint32_t*)nullptr,
-                     (const uint32_t*)(zn + 2));
+                     nullptr, (const uint32_t*)nullptr, parent, nullptr, nullptr, nullptr,
+                     has_anchor ? 0u : INV, (const uint32_t*)nullptr, (const uint32_t*)(zn + 2));
 }
 
 __global__ void k_add_u32(uint32_t* p, uint64_t n, uint32_t d) {

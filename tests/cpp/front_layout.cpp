@@ -2,12 +2,14 @@
 // every table inside [0, total), no two tables of a layout overlapping, u64 tables at even
 // words, u16 entry arrays at multiples of 4 words with 8 entries of room behind their last
 // entry, and every offset and total equal to what the size formulas and the launchers' pointer
-// arithmetic gave before the layouts existed (frozen below, base address 0).  Prints "ok".
+// arithmetic gave before the layouts existed (frozen below, base address 0).  The radix sort's
+// layout (rsort_layout) the same way, over record counts n.  Prints "ok".
 #include <stdint.h>
 #include <stdio.h>
 
 #include <algorithm>
 #include <cmath>
+#include <random>
 #include <vector>
 
 #include "front_layout.h"
@@ -131,6 +133,22 @@ static Fh carve_fh(uint64_t m, uint32_t NB) {
   r.epx = up(r.bx + 8 * ((uint64_t)NB + 2), 16);
   return r;
 }
+// The radix sort's tmp: the size formula (its flat-scan term included), and the sort's carving
+// from an 8-byte-aligned base (uintptr_t arithmetic on base + 4 * words).
+constexpr uint64_t RSTILE = 8192;
+static size_t rsort_tmp_words(uint64_t n) {
+  uint64_t nt = (n + RSTILE - 1) / RSTILE;
+  return 512 * nt + std::max<size_t>(scan_words(512 * nt), 512 * ((nt + TMG - 1) / TMG) + 1030);
+}
+struct Rsort { uint64_t counts, gsum, dstart; };
+static Rsort carve_rsort(uint64_t n, uint64_t base) {
+  uint64_t nt = (n + RSTILE - 1) / RSTILE;
+  Rsort r;
+  r.counts = 0;
+  r.gsum = 4 * (512 * nt);
+  r.dstart = ((base + r.gsum + 4 * (512 * ((nt + TMG - 1) / TMG)) + 7) & ~(uint64_t)7) - base;
+  return r;
+}
 }  // namespace ref
 
 // A table of a layout: [off, off + len) words; kind 1: u32, 2: u64, 3: u16 entries (len covers
@@ -156,6 +174,26 @@ static uint64_t ep_words(uint64_t entries) { return (entries + 8 + 1) / 2; }
 #define SAME(field, refbytes)                                                                  \
   CHECK((uint64_t)(field) * 4 == (refbytes), #field " %llu words, before %llu bytes (m=%llu n=%u)", \
         (unsigned long long)(field), (unsigned long long)(refbytes), (unsigned long long)m, n)
+
+// rsort_layout(n) against the former size formula and carving; containment, order, alignment.
+static void check_rsort(uint64_t m) {
+  const uint32_t n = 0;  // (the messages' id count: none here)
+  const RsortLayout L = rsort_layout(m);
+  const uint64_t nt = (m + ref::RSTILE - 1) / ref::RSTILE, ng = (nt + ref::TMG - 1) / ref::TMG;
+  CHECK(L.ntiles == nt, "rsort ntiles %llu (n=%llu)", (unsigned long long)L.ntiles, (unsigned long long)m);
+  CHECK(L.total == ref::rsort_tmp_words(m), "rsort total %zu, before %zu (n=%llu)", L.total,
+        ref::rsort_tmp_words(m), (unsigned long long)m);
+  for (uint64_t base : {0ull, 256ull, 0x7f0000000008ull}) {
+    const ref::Rsort r = ref::carve_rsort(m, base);
+    SAME(L.counts, r.counts);
+    SAME(L.gsum, r.gsum);
+    SAME(L.dstart, r.dstart);
+  }
+  check_arrays("rsort", m, n,
+               {{"counts", L.counts, 512 * nt, 1}, {"gsum", L.gsum, 512 * ng, 1},
+                {"dstart", L.dstart, 2 * 513, 2}},
+               L.total);
+}
 
 int main() {
   const uint32_t ns[] = {1, 2, 1023, 1024, 1025, 1u << 20, 3000017, 1u << 25, (1u << 25) + 1,
@@ -249,6 +287,23 @@ int main() {
                      F.total);
       }
     }
+  {  // the sort: n = 0 and 1, around every multiple of RS_TILE and of RS_TILE * TM_G up to
+     // 2^32 - 1 records, the largest n, and random n (uniform, and uniform in magnitude)
+    static_assert(RS_TILE == ref::RSTILE && TM_G == ref::TMG, "frozen constants");
+    const uint64_t NMAX = (1ull << 32) - 1, T = ref::RSTILE, GT = ref::RSTILE * ref::TMG;
+    auto around = [&](uint64_t c) {
+      for (int d = -2; d <= 2; ++d)
+        if ((d >= 0 || c >= (uint64_t)-d) && c + d <= NMAX) check_rsort(c + d);
+    };
+    check_rsort(0);
+    check_rsort(1);
+    for (uint64_t c = T; c <= NMAX; c += T) around(c);
+    for (uint64_t c = GT; c <= NMAX; c += GT) around(c);
+    around(NMAX);
+    std::mt19937_64 rng(12345);
+    for (int i = 0; i < 4000; ++i) check_rsort(rng() % (NMAX + 1));
+    for (int i = 0; i < 1000; ++i) check_rsort(rng() % (1ull << (10 + i % 22)));
+  }
   if (fails) {
     fprintf(stderr, "%d checks failed\n", fails);
     return 1;

@@ -1,5 +1,5 @@
-"""The degree passes' scratch layouts (sheep_amd/csrc/front_layout.h): every table inside its
-buffer, none overlapping, u64 and 16-byte alignment, the room behind the u16 entry arrays, and
+"""The degree passes' and the radix sort's scratch layouts (sheep_amd/csrc/front_layout.h):
+every table inside its buffer, none overlapping, u64 and 16-byte alignment, the room behind the u16 entry arrays, and
 every offset and total equal to the size formulas and launcher pointer arithmetic the layouts
 replaced (frozen in tests/cpp/front_layout.cpp).  Host code only (g++), no GPU, no library."""
 import os

@@ -80,6 +80,20 @@ def test_rmat_generator_and_tree(oracle, api, gpu, scale, seed):
     assert np.array_equal(w_d[:n].cpu().numpy().view(np.uint32), w)
 
 
+@pytest.mark.parametrize("scale,seed", [(14, 7), (17, 8)])
+def test_explicit_sequence_tree_partitioned_gathers(oracle, api, options, scale, seed):
+    """The explicit-sequence tree with the partitioned rank gathers feeding the plain two-pass
+    sort (edge_part=1: otherwise taken only from 2^22 records): the edge pass reads k_part's
+    records and counts the first radix pass's digits, 8 bits wide at scale 14 and 9 at scale 17.
+    parent and pst bit-exact against the checker."""
+    from sheep_amd import capi
+
+    options(edge_part=1)
+    uv = oracle.rmat(scale, 16, seed)
+    check_tree(oracle, api, uv, oracle.degree_sequence(uv))
+    assert "partition" in dict(capi.last_timings())
+
+
 def _degrees(case, rng):
     if case == "heavy":     # zipf tail: every counting class, hundreds of ids above 1024
         d = np.minimum(rng.zipf(1.6, 300001), 1 << 31).astype(np.uint32)

@@ -135,6 +135,6 @@ def test_sparse_star_spacings():
 def test_loop_constants_match_the_source():
     """The spacings and sizes are built around three constants of sheep_kernels.hip."""
     src = open(os.path.join(ROOT, "sheep_amd", "csrc", "sheep_kernels.hip")).read()
-    assert int(re.search(r"const uint32_t scan_limit = (\d+);", src).group(1)) == gf.SCAN_LIMIT
+    assert int(re.search(r"constexpr uint32_t KB_SCAN_LIMIT = (\d+);", src).group(1)) == gf.SCAN_LIMIT
     assert int(re.search(r"constexpr uint32_t KM_WIN = (\d+);", src).group(1)) == gf.KM_WIN
     assert int(re.search(r"constexpr int KM_CHUNK = (\d+);", src).group(1)) == gf.KM_CHUNK
