@@ -26,6 +26,11 @@
  * degree pass counts endpoints with record offsets beyond 2^31 records (the fused pass of
  * graph2tree); the partition evaluation sorts at most 2^31 adjacency entries per pass and
  * beyond that walks id ranges, so only a single vertex with more than 2^31 entries is refused.
+ * The tree certificate and the tree facts take n_seq < 2^31 ranks (the Euler tour has 2 n_seq
+ * arcs, indexed by u32).
+ *
+ * ABI 1.1 adds sheep_verify_tree_dev, sheep_verify_tree and sheep_tree_facts_dev; nothing else
+ * changed.
  */
 #ifndef SHEEP_AMD_H
 #define SHEEP_AMD_H
@@ -297,6 +302,44 @@ int sheep_partition_edges_dev(const uint32_t* d_uv, uint64_t m, const int16_t* d
 int sheep_partition_edges(const uint32_t* edges_uv, uint64_t m, const int16_t* parts,
                           uint32_t n_parts_vid, const uint32_t* seq, uint32_t n_seq, uint32_t n_parts,
                           uint32_t* out_uv, uint64_t* part_start);
+
+/* ---- tree certificate and tree facts (ABI 1.1) ---------------------------------------------
+ * sheep_verify_tree_dev: is (d_parent, d_pst) the elimination tree of the m records under the
+ * rank map d_rank (n_ids entries, INVALID outside seq)?  Linear work on the device, no oracle,
+ * no walk along parent pointers (replaces JTree::isValid, jtree.h:84-102, which is O(m * height)
+ * and accepts forests that are not the elimination tree).  In rank space, a forest in heap
+ * order is the elimination tree iff (A) the higher end of every record is an ancestor of its
+ * lower end, and (B) every non-root v has a witness: a record (x, parent[v]) with x in v's
+ * subtree.  pst is checked against the build's rule: pst[r] = the non-self-loop records whose
+ * lower-rank end is r, a record that leaves seq counted at its end in seq.
+ * report (host, 8 words; every count exact):
+ *   [0] heap-order violations: parent[v] neither INVALID nor in (v, n_seq)
+ *   [1] records that violate (A)
+ *   [2] non-roots without a witness (B); a record that violates (A) witnesses nothing
+ *   [3] ranks whose pst differs from the recount (0 when d_pst is NULL: not checked)
+ *   [4] the smallest rank in any violation (v for [0], [2], [3]; the lower end for [1]), or
+ *       SHEEP_INVALID
+ *   [5..7] 0
+ * If [0] != 0 nothing that follows parent pointers runs (a cycle is possible): [1..3] are
+ * UINT64_MAX, "not computed", and [4] is the smallest heap-violating rank.
+ * Returns SHEEP_OK whenever the check ran, whatever it found.  -EINVAL: a null argument,
+ * m >= 2^32 (both before any device is touched) or n_seq >= 2^31; -ERANGE as
+ * sheep_build_tree_dev (an id >= n_ids beside an end in seq), and for a rank >= n_seq.
+ * n_seq == 0: an all-zero report.  Synchronises the stream. */
+int sheep_verify_tree_dev(const uint32_t* d_uv, uint64_t m, const uint32_t* d_rank, uint32_t n_ids,
+                          uint32_t n_seq, const uint32_t* d_parent, const uint32_t* d_pst,
+                          uint64_t* report, void* stream);
+/* The same from host arrays (pst nullable): uploads them (or uses the registered device copy of
+ * (edges_uv, m)), builds the rank map from seq (-EINVAL if seq repeats an id; ids beyond
+ * max(seq) are outside it, as in sheep_build_tree) and verifies. */
+int sheep_verify_tree(const uint32_t* edges_uv, uint64_t m, const uint32_t* seq, uint32_t n_seq,
+                      const uint32_t* parent, const uint32_t* pst, uint64_t* report);
+/* JNodeTable::getFacts (jnode.cpp:256-290) of a tree in HBM, without a walk: out (host, 9
+ * words) = width, roots, vheight, eheight, verts, edges, halo, core, fill in TREEFAQS print
+ * order; halo and core are jnids (0xFFFFFFFF: none).  -EINVAL: a null argument, n >= 2^31, or a
+ * forest that is not in heap order.  Synchronises the stream. */
+int sheep_tree_facts_dev(const uint32_t* d_parent, const uint32_t* d_pst, uint32_t n,
+                         uint64_t* out, void* stream);
 
 /* The whole single-device hot path: degree -> sequence -> tree (graph2tree's Sorted+Mapped).
  * d_seq holds n_ids entries, d_parent/d_pst hold n_ids entries (n_seq used).  Synchronises. */

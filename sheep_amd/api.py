@@ -174,6 +174,33 @@ def merge_trees(a, b):
     return JNodeTable(parent[:n], pst[:n])
 
 
+def verify_tree(uv, seq, tree, check_pst=True):
+    """Certify ``tree`` as the elimination tree of the records under ``seq`` on the GPU
+    (sheep_verify_tree; what JTree::certify and graph2tree -c call).  Returns the report as a
+    dict (sheep_amd.capi.report_dict): ``valid``, the four violation counts, ``first``."""
+    uv = _as_edges(uv)
+    seq = np.ascontiguousarray(seq, np.uint32)
+    if tree.size() != seq.size:
+        raise SheepError(-errno.EINVAL, "verify_tree: tree and sequence of different sizes")
+    out = np.zeros(8, np.uint64)
+    capi.call("sheep_verify_tree", _ptr(uv), uv.shape[0], _ptr(seq), seq.size, _ptr(tree.parent),
+              _ptr(tree.pst) if check_pst else None, _ptr(out))
+    return capi.report_dict(out)
+
+
+def tree_facts(tree):
+    """JNodeTable::getFacts (TREEFAQS) on the GPU: uploads parent and pst_weight and reduces them
+    there (sheep_tree_facts_dev).  A dict: width, roots, vheight, eheight, verts, edges, halo,
+    core, fill."""
+    import torch
+
+    from . import device
+
+    parent = torch.from_numpy(tree.parent).to("cuda")
+    pst = torch.from_numpy(tree.pst).to("cuda")
+    return device.tree_facts(parent, pst)
+
+
 def graph2tree(uv, mode=DEGREE_LLAMA):
     """graph2tree's serial path (graph2tree.cpp:162-193): degreeSequence + JTree."""
     seq = degree_sequence(uv, mode)

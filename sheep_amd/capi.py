@@ -106,6 +106,10 @@ def lib():
         "sheep_records_load_dat": [c.c_char_p, c.c_uint64, c.c_uint64, u32p, c.c_uint64, vp, vp],
         "sheep_read_dat_dev": [c.c_char_p, c.c_uint64, c.c_uint64, u32p, c.c_uint64, vp, vp, vp],
         "sheep_get_option": [c.c_char_p, c.c_void_p],
+        "sheep_verify_tree_dev": [u32p, c.c_uint64, u32p, c.c_uint32, c.c_uint32, u32p, u32p, vp,
+                                  vp],
+        "sheep_verify_tree": [u32p, c.c_uint64, u32p, c.c_uint32, u32p, u32p, vp],
+        "sheep_tree_facts_dev": [u32p, u32p, c.c_uint32, vp, vp],
         "sheep_partition": [u32p, u32p, c.c_uint32, u32p, vp, c.c_uint32, c.c_double, vp,
                             c.c_uint32, vp],
     }
@@ -143,3 +147,19 @@ def set_option(name, value):
     call("sheep_get_option", name.encode(), ctypes.byref(old))
     call("sheep_set_option", name.encode(), int(value))
     return old.value
+
+
+REPORT_KEYS = ("heap", "ancestor", "witness", "pst", "first")
+NOT_COMPUTED = 0xFFFFFFFFFFFFFFFF
+
+
+def report_dict(words):
+    """The 8 report words of sheep_verify_tree* as a dict: the counts of heap-order violations,
+    records whose higher end is no ancestor of the lower, non-roots without a witness, pst
+    mismatches (NOT_COMPUTED for the last three after a heap violation), ``first`` the smallest
+    rank in any violation (INVALID: none), ``valid`` and the raw ``words``."""
+    w = [int(x) for x in words]
+    d = dict(zip(REPORT_KEYS, w))
+    d["valid"] = not any(w[:4])
+    d["words"] = w
+    return d

@@ -22,6 +22,7 @@
 #include "../../include/sheep_amd.h"
 #include "sheep_comm.h"
 #include "sheep_internal.h"
+#include "verify_layout.h"
 
 namespace sheep {
 
@@ -1963,7 +1964,7 @@ static void require_aligned(const void* p, const char* what) {
 
 extern "C" {
 
-int sheep_abi_version(void) { return (1 << 16) | 0; }
+int sheep_abi_version(void) { return (1 << 16) | 1; }  // 1.1: sheep_verify_tree*, sheep_tree_facts_dev
 
 const char* sheep_last_error(void) { return g_last_error.c_str(); }
 
@@ -2233,6 +2234,129 @@ static void partition_edges_dev(Ctx& c, const uint32_t* d_uv, uint64_t m, const 
                          dstart, c.d_err, s);
   HIP_CHECK(hipMemcpyAsync(part_start, dstart, ((size_t)n_parts + 1) * 8, hipMemcpyDeviceToHost, s));
   check_err(c, s);  // synchronises; -ERANGE for an id outside the sequence or a vertex without part
+}
+
+// ---- tree certificate and tree facts (sheep_verify.hip) -------------------------------------
+
+static std::vector<unsigned long long> vf_read_ws(const unsigned long long* ws, hipStream_t s) {
+  std::vector<unsigned long long> h(VF_WS_WORDS);
+  HIP_CHECK(hipMemcpyAsync(h.data(), ws, VF_WS_WORDS * 8, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  return h;
+}
+
+// Heap check (resets the counters); the counter words on the host.  Synchronises.
+static std::vector<unsigned long long> vf_heap(Ctx& c, const uint32_t* d_parent, uint32_t n,
+                                               unsigned long long** ws_out, hipStream_t s) {
+  if (n >= (1u << 31)) throw ApiError(-EINVAL, "tree verifier: at most 2^31 - 1 ranks (2n arcs)");
+  unsigned long long* ws = (unsigned long long*)c.scratch.get("vf_ws", VF_WS_WORDS * 8);
+  launch_vf_heap(d_parent, n, ws, s);
+  *ws_out = ws;
+  return vf_read_ws(ws, s);
+}
+
+// Children lists, Euler tour and tour positions of a forest that passed the heap check.
+static VfTour vf_tour(Ctx& c, const uint32_t* d_parent, uint32_t n, hipStream_t s) {
+  Scratch& sc = c.scratch;
+  VfTour T;
+  T.n = n;
+  uint64_t* items = (uint64_t*)sc.get("vf_items", (size_t)n * 8);
+  uint64_t* items_b = (uint64_t*)sc.get("vf_items_b", (size_t)n * 8);
+  uint32_t* rtmp = (uint32_t*)sc.get("vf_rsort_tmp", rsort_tmp_words(n) * 4);
+  T.kfirst = (uint32_t*)sc.get("vf_kfirst", ((size_t)n + 1) * 4);
+  T.klast = (uint32_t*)sc.get("vf_klast", ((size_t)n + 1) * 4);
+  T.cells_a = (uint64_t*)sc.get("vf_cells_a", (size_t)n * 16);
+  T.cells_b = (uint64_t*)sc.get("vf_cells_b", (size_t)n * 16);
+  T.tt = (uint2*)sc.get("vf_tt", (size_t)n * 8);
+  T.ktin = (uint32_t*)sc.get("vf_ktin", (size_t)n * 4);
+  launch_vf_items(d_parent, n, items, s);
+  T.kids = radix_sort_u64(items, items_b, items, n, 0, bits_for(n), rtmp, s, false);
+  launch_vf_tour(T, s);
+  return T;
+}
+
+static void verify_tree_dev(Ctx& c, const uint32_t* d_uv, uint64_t m, const uint32_t* d_rank,
+                            uint32_t n_ids, uint32_t n_seq, const uint32_t* d_parent,
+                            const uint32_t* d_pst, uint64_t* report, hipStream_t s) {
+  for (int i = 0; i < 8; ++i) report[i] = 0;
+  if (n_seq == 0) return;
+  Timer tm(s);
+  unsigned long long* ws;
+  std::vector<unsigned long long> h = vf_heap(c, d_parent, n_seq, &ws, s);
+  tm.mark("vf_heap");
+  if (h[VF_HEAP] == 0) {
+    const VfTour T = vf_tour(c, d_parent, n_seq, s);
+    tm.mark("vf_tour");
+    uint32_t* cnt = nullptr;
+    if (d_pst) {
+      cnt = (uint32_t*)c.scratch.get("vf_cnt", (size_t)n_seq * 4);
+      HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)n_seq * 4, s));
+    }
+    uint8_t* witness = (uint8_t*)c.scratch.get("vf_witness", n_seq);
+    HIP_CHECK(hipMemsetAsync(witness, 0, n_seq, s));
+    launch_vf_records(d_uv, m, d_rank, n_ids, d_parent, T, cnt, witness, ws, c.d_err, s);
+    tm.mark("vf_records");
+    launch_vf_final(d_parent, d_pst, cnt, witness, n_seq, ws, s);
+    tm.mark("vf_final");
+    h = vf_read_ws(ws, s);
+    check_err(c, s);  // -ERANGE as the tree build
+  }
+  tm.finish(c);
+  vf_report(report, h[VF_HEAP], h[VF_A], h[VF_B], h[VF_PST], (uint32_t)h[VF_MIN]);
+}
+
+static void tree_facts_dev(Ctx& c, const uint32_t* d_parent, const uint32_t* d_pst, uint32_t n,
+                           uint64_t* out, hipStream_t s) {
+  for (int i = 0; i < 9; ++i) out[i] = 0;
+  out[6] = out[7] = INV;  // halo, core: none (jnid_t INVALID)
+  if (n == 0) return;
+  Timer tm(s);
+  unsigned long long* ws;
+  std::vector<unsigned long long> h = vf_heap(c, d_parent, n, &ws, s);
+  tm.mark("vf_heap");
+  if (h[VF_HEAP]) throw ApiError(-EINVAL, "tree facts: forest not heap-ordered");
+  const VfTour T = vf_tour(c, d_parent, n, s);
+  tm.mark("vf_tour");
+  long long* sums = (long long*)c.scratch.get("vf_scan_sums", vf_scan_tiles(n) * 8);
+  launch_vf_facts(T, d_pst, (long long*)T.cells_a, (long long*)T.cells_b, sums, ws, s);
+  tm.mark("vf_facts");
+  h = vf_read_ws(ws, s);
+  tm.finish(c);
+  // TREEFAQS print order (JNodeTable::Facts, lib/jnode.h).  core: the first id whose width
+  // reaches the running maximum, which already includes that id, is id 0; fill sums
+  // width - pst_weight - 1, which is 0 for every node (width = 1 + pst_weight).
+  out[0] = h[VF_WIDTH];
+  out[1] = h[VF_ROOTS];
+  out[2] = h[VF_VH];
+  out[3] = h[VF_EH];
+  out[4] = n;
+  out[5] = h[VF_EDGES];
+  out[6] = (uint32_t)h[VF_HALO];
+  out[7] = 0;
+  out[8] = 0;
+}
+
+int sheep_verify_tree_dev(const uint32_t* d_uv, uint64_t m, const uint32_t* d_rank, uint32_t n_ids,
+                          uint32_t n_seq, const uint32_t* d_parent, const uint32_t* d_pst,
+                          uint64_t* report, void* stream) {
+  API_BEGIN
+  if (!report || (m && !d_uv) || (n_ids && !d_rank) || (n_seq && !d_parent))
+    throw ApiError(-EINVAL, "sheep_verify_tree_dev: null argument");
+  require_records(m, "tree verifier");
+  Ctx& c = ctx();
+  require_aligned(d_uv, "d_uv");
+  verify_tree_dev(c, d_uv, m, d_rank, n_ids, n_seq, d_parent, d_pst, report, pick(c, stream));
+  API_END
+}
+
+int sheep_tree_facts_dev(const uint32_t* d_parent, const uint32_t* d_pst, uint32_t n, uint64_t* out,
+                         void* stream) {
+  API_BEGIN
+  if (!out || (n && (!d_parent || !d_pst)))
+    throw ApiError(-EINVAL, "sheep_tree_facts_dev: null argument");
+  Ctx& c = ctx();
+  tree_facts_dev(c, d_parent, d_pst, n, out, pick(c, stream));
+  API_END
 }
 
 // ---- records resident in HBM ---------------------------------------------------------------
@@ -2841,6 +2965,36 @@ int sheep_build_tree(const uint32_t* edges_uv, uint64_t m, const uint32_t* seq, 
   HIP_CHECK(hipMemcpyAsync(parent_out, parent, (size_t)n_seq * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipMemcpyAsync(pst_out, pst, (size_t)n_seq * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
+  API_END
+}
+
+int sheep_verify_tree(const uint32_t* edges_uv, uint64_t m, const uint32_t* seq, uint32_t n_seq,
+                      const uint32_t* parent, const uint32_t* pst, uint64_t* report) {
+  API_BEGIN
+  if (!report || (m && !edges_uv) || (n_seq && (!seq || !parent)))
+    throw ApiError(-EINVAL, "sheep_verify_tree: null argument");
+  require_records(m, "tree verifier");
+  for (int i = 0; i < 8; ++i) report[i] = 0;
+  if (n_seq == 0) return SHEEP_OK;
+  Ctx& c = ctx();
+  hipStream_t s = c.stream;
+  const size_t nb = (size_t)n_seq * 4;
+  uint32_t n_rank = *std::max_element(seq, seq + n_seq) + 1;  // as sheep_build_tree
+  uint32_t* uv = upload_records(c, edges_uv, m, s);
+  uint32_t* dseq = (uint32_t*)c.scratch.get("h_seq", nb);
+  HIP_CHECK(hipMemcpyAsync(dseq, seq, nb, hipMemcpyHostToDevice, s));
+  uint32_t* rank = (uint32_t*)c.scratch.get("rank", (size_t)n_rank * 4);
+  launch_fill(rank, INV, n_rank, s);
+  launch_rank_scatter(dseq, n_seq, rank, c.d_err, s);
+  check_err(c, s);
+  uint32_t* dparent = (uint32_t*)c.scratch.get("h_parent", nb);
+  HIP_CHECK(hipMemcpyAsync(dparent, parent, nb, hipMemcpyHostToDevice, s));
+  uint32_t* dpst = nullptr;
+  if (pst) {
+    dpst = (uint32_t*)c.scratch.get("h_pst", nb);
+    HIP_CHECK(hipMemcpyAsync(dpst, pst, nb, hipMemcpyHostToDevice, s));
+  }
+  verify_tree_dev(c, uv, m, rank, n_rank, n_seq, dparent, dpst, report, s);
   API_END
 }
 

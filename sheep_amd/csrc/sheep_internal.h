@@ -386,6 +386,40 @@ void launch_partition_edges(const uint32_t* uv, uint64_t m, const int16_t* parts
                             uint32_t n_ids, uint32_t n_parts, uint64_t* items, uint64_t* items_b,
                             uint32_t* rtmp, uint32_t* out, unsigned long long* pstart, uint32_t* err,
                             hipStream_t s);
+// Tree certificate and tree facts (sheep_verify.hip; index arithmetic in verify_layout.h).
+// The counter words (ws: VF_WS_WORDS u64, reset by launch_vf_heap): violation counts, the
+// smallest rank in any violation (low word; INV: none), then the facts' reductions.
+enum { VF_HEAP = 0, VF_A, VF_B, VF_PST, VF_MIN, VF_ROOTS, VF_WIDTH, VF_EDGES, VF_HALO, VF_VH, VF_EH,
+       VF_WS_WORDS = 16 };
+// Children lists and Euler tour of a heap-ordered forest over n ranks (n < 2^31: 2n arcs).
+struct VfTour {
+  uint32_t n = 0;
+  uint64_t* kids = nullptr;     // n: (parent << 32 | v) sorted by parent (roots under parent n)
+  uint32_t* kfirst = nullptr;   // n + 1: first slot of a parent's children (INV: none)
+  uint32_t* klast = nullptr;    // n + 1: their last slot
+  uint64_t* cells_a = nullptr;  // 2n each: the list ranking's double buffer
+  uint64_t* cells_b = nullptr;
+  uint2* tt = nullptr;          // n: (tin, tout) tour positions per rank
+  uint32_t* ktin = nullptr;     // n: tin of the child in each slot
+};
+// Resets ws, then counts heap-order violations (VF_HEAP, VF_MIN) and roots (VF_ROOTS).
+void launch_vf_heap(const uint32_t* parent, uint32_t n, unsigned long long* ws, hipStream_t s);
+void launch_vf_items(const uint32_t* parent, uint32_t n, uint64_t* items, hipStream_t s);
+// From T.kids (sorted): everything else of T.  Only for a forest that passed launch_vf_heap.
+void launch_vf_tour(const VfTour& T, hipStream_t s);
+// Per record: the pst recount into cnt (nullable; n zeroed words), (A) into VF_A / VF_MIN, the
+// witness bytes (n, zeroed).  ERR_RANGE as the edge pass, and for a rank >= n.
+void launch_vf_records(const uint32_t* uv, uint64_t m, const uint32_t* rank, uint32_t n_ids,
+                       const uint32_t* parent, const VfTour& T, uint32_t* cnt, uint8_t* witness,
+                       unsigned long long* ws, uint32_t* err, hipStream_t s);
+// Per rank: non-roots without witness (VF_B), pst != cnt (VF_PST; pst nullable), VF_MIN.
+void launch_vf_final(const uint32_t* parent, const uint32_t* pst, const uint32_t* cnt,
+                     const uint8_t* witness, uint32_t n, unsigned long long* ws, hipStream_t s);
+// VF_WIDTH .. VF_EH from the tour and pst.  wv / we: 2n i64 each (T.cells_a / cells_b are free
+// once launch_vf_tour is done); sums: vf_scan_tiles(n) i64.
+size_t vf_scan_tiles(uint32_t n);
+void launch_vf_facts(const VfTour& T, const uint32_t* pst, long long* wv, long long* we,
+                     long long* sums, unsigned long long* ws, hipStream_t s);
 // XS1 records {u32 tail, u32 head, f32 weight} -> (tail, head) pairs; max id + 1 into *max_id.
 void launch_strip_xs1(const uint32_t* raw, uint64_t n, uint32_t* uv, uint32_t* max_id, hipStream_t s);
 void launch_merge(uint32_t* parent_a, uint32_t* pst_a, const uint32_t* parent_b,

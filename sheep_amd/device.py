@@ -190,6 +190,31 @@ def evaluate(uv, parts, rank, n_parts=None):
     return dict(zip(EVAL_KEYS, (int(x) for x in out)))
 
 
+FACT_KEYS = ("width", "roots", "vheight", "eheight", "verts", "edges", "halo", "core", "fill")
+report_dict = capi.report_dict
+
+
+def verify_tree(uv, rank, n_seq, parent, pst=None):
+    """Certify (parent, pst) as the elimination tree of the records ``uv`` under the rank map
+    ``rank`` (sheep_verify_tree_dev; all tensors on the device).  ``pst`` None: not checked."""
+    import numpy as np
+
+    out = np.zeros(8, np.uint64)
+    capi.call("sheep_verify_tree_dev", _p(uv), uv.shape[0], _p(rank), rank.numel(), n_seq,
+              _p(parent), _p(pst), ctypes.c_void_p(out.ctypes.data), _stream())
+    return report_dict(out)
+
+
+def tree_facts(parent, pst):
+    """TREEFAQS of a tree in HBM (sheep_tree_facts_dev): a dict (FACT_KEYS)."""
+    import numpy as np
+
+    out = np.zeros(9, np.uint64)
+    capi.call("sheep_tree_facts_dev", _p(parent), _p(pst), parent.numel(),
+              ctypes.c_void_p(out.ctypes.data), _stream())
+    return dict(zip(FACT_KEYS, (int(x) for x in out)))
+
+
 def graph2tree(uv, n_ids, mode=capi.DEGREE_LLAMA, seq=None, parent=None, pst=None):
     dev = uv.device
     seq = seq if seq is not None else torch.empty(max(n_ids, 1), dtype=torch.uint32, device=dev)

@@ -101,6 +101,22 @@ class JTree {
     return true;
   }
 
+  // Certificate on the GPU (sheep_verify_tree): true iff this table is THE elimination tree of
+  // the graph's records under seq, pst_weight included.  Linear work whatever the height, so it
+  // runs at full size, and unlike isValid it rejects a heap-ordered forest that merely keeps
+  // every higher endpoint above the lower one.  report: the 8 words of include/sheep_amd.h.
+  template <typename GraphType>
+  bool certify(GraphType const& graph, std::vector<vid_t> const& seq, uint64_t report[8]) const {
+    if (seq.size() != size()) throw std::invalid_argument("certify: sequence and tree sizes differ");
+    graph.to_device();
+    std::vector<jnid_t> parent = jnodes.parents();
+    std::vector<esize_t> pst = jnodes.psts();
+    sheep_check(sheep_verify_tree(graph.records_data(), graph.records(), seq.data(),
+                                  (uint32_t)seq.size(), parent.data(), pst.data(), report),
+                "JTree::certify");
+    return report[0] == 0 && report[1] == 0 && report[2] == 0 && report[3] == 0;
+  }
+
  private:
   void make_index(std::vector<vid_t> const& seq) {
     if (seq.empty()) return;
