@@ -30,7 +30,8 @@
  * arcs, indexed by u32).
  *
  * ABI 1.1 adds sheep_verify_tree_dev, sheep_verify_tree and sheep_tree_facts_dev; nothing else
- * changed.
+ * changed.  ABI 1.2 adds sheep_read_net_dev and sheep_records_load_net (SNAP text parsed on the
+ * device) and the option net_chunk; nothing else changed.
  */
 #ifndef SHEEP_AMD_H
 #define SHEEP_AMD_H
@@ -77,6 +78,26 @@ int sheep_records_load_dat(const char* path, uint64_t part, uint64_t num_parts, 
 int sheep_read_dat_dev(const char* path, uint64_t part, uint64_t num_parts, uint32_t* d_uv,
                        uint64_t cap, uint64_t* m_out, uint32_t* max_id_out, void* stream);
 
+/* ---- SNAP text (.net) ingest (ABI 1.2) -------------------------------------------------------
+ * The twins of the two .dat calls for a text file of whitespace-separated unsigned pairs.  The
+ * record stream is exactly the one SNAPReader yields (`std::istream >> unsigned` pairs in the C
+ * locale, lib/readerwriter.h): the text goes through pinned staging to HBM in chunks (option
+ * net_chunk) and is tokenised and converted there.  The device parses the maximal prefix of
+ * regular tokens (all decimal digits, value <= 0xFFFFFFFF); from the first byte of the first
+ * other token (a sign, a letter, '#', '.', NUL, an overflow, or a token longer than a chunk) the
+ * library runs `>>` itself on the host and appends its values, so "4+5", "-1" or "12abc" give
+ * what the reference gives.  The values in pairs are the records; an odd last value is dropped.
+ * d_uv / uv_out NULL is the size query, a count pass over the whole file (the file size does not
+ * give the count); part/num_parts, cap, *m_out and *max_id_out as for .dat.  Both synchronise.
+ * -EINVAL: a null path or a part outside [1, num_parts]; -ENOENT: the file cannot be opened
+ * (all three before any device is touched); -ERANGE: cap below the range's records, or an id
+ * 0xFFFFFFFE / 0xFFFFFFFF in the range; -EINVAL: 2^32 or more records; -EBUSY: uv_out already
+ * registered.  Release sheep_records_load_net's copy with sheep_records_release(uv_out). */
+int sheep_read_net_dev(const char* path, uint64_t part, uint64_t num_parts, uint32_t* d_uv,
+                       uint64_t cap, uint64_t* m_out, uint32_t* max_id_out, void* stream);
+int sheep_records_load_net(const char* path, uint64_t part, uint64_t num_parts, uint32_t* uv_out,
+                           uint64_t cap, uint64_t* m_out, uint32_t* max_id_out);
+
 /* Free all device scratch held by the library on the current device. */
 int sheep_release(void);
 
@@ -91,7 +112,8 @@ int sheep_abi_version(void);
  * variables, read ONCE when the library first initialises a device; afterwards only these
  * calls change them (process-wide).  Names: degree, edge_part, part_overlap, kb_buckets,
  * kb_rankb, kb_merge, kb_pipe, tree_stats, bin_direct, bin_slack, kb_gsum, eval_pass,
- * ls_split, ls_seq.
+ * ls_split, ls_seq, net_chunk (bytes of text per chunk of the .net ingest: default 32 MiB, kept
+ * in [4096, 2^30] and a multiple of 16 whatever is set).
  * -EINVAL for an unknown name. */
 int sheep_set_option(const char* name, long long value);
 int sheep_get_option(const char* name, long long* value);

@@ -105,6 +105,8 @@ def lib():
         "sheep_records_release": [u32p],
         "sheep_records_load_dat": [c.c_char_p, c.c_uint64, c.c_uint64, u32p, c.c_uint64, vp, vp],
         "sheep_read_dat_dev": [c.c_char_p, c.c_uint64, c.c_uint64, u32p, c.c_uint64, vp, vp, vp],
+        "sheep_records_load_net": [c.c_char_p, c.c_uint64, c.c_uint64, u32p, c.c_uint64, vp, vp],
+        "sheep_read_net_dev": [c.c_char_p, c.c_uint64, c.c_uint64, u32p, c.c_uint64, vp, vp, vp],
         "sheep_get_option": [c.c_char_p, c.c_void_p],
         "sheep_verify_tree_dev": [u32p, c.c_uint64, u32p, c.c_uint32, c.c_uint32, u32p, u32p, vp,
                                   vp],

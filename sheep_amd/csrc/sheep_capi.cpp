@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <fstream>
 #include <memory>
 #include <chrono>
 #include <mutex>
@@ -22,6 +23,7 @@
 #include "../../include/sheep_amd.h"
 #include "sheep_comm.h"
 #include "sheep_internal.h"
+#include "net_layout.h"
 #include "verify_layout.h"
 
 namespace sheep {
@@ -48,7 +50,13 @@ static const KnobDef kKnobs[] = {
     {"kb_merge", &Knobs::kb_merge},       {"ff_groups", &Knobs::ff_groups},
     {"kb_rlink", &Knobs::kb_rlink},
     {"kb_fresh_lo", &Knobs::kb_fresh_lo}, {"kb_fresh_hi", &Knobs::kb_fresh_hi},
+    {"net_chunk", &Knobs::net_chunk},
 };
+
+// What an option is stored as: net_chunk is kept inside its range (net_layout.h).
+static int knob_value(const KnobDef& d, long long v) {
+  return d.field == &Knobs::net_chunk ? (int)net_chunk_clamp(v) : (int)v;
+}
 
 static Knobs g_knobs;
 static std::once_flag g_knobs_once;
@@ -62,7 +70,7 @@ static void load_knobs_from_env() {
     if (d.field == &Knobs::degree)  // "atomic" / "bucketed" (or the number)
       g_knobs.degree = !strcmp(v, "atomic") ? 1 : !strcmp(v, "bucketed") ? 2 : atoi(v);
     else
-      g_knobs.*d.field = atoi(v);
+      g_knobs.*d.field = knob_value(d, atoll(v));
   }
 }
 
@@ -1964,7 +1972,8 @@ static void require_aligned(const void* p, const char* what) {
 
 extern "C" {
 
-int sheep_abi_version(void) { return (1 << 16) | 1; }  // 1.1: sheep_verify_tree*, sheep_tree_facts_dev
+// 1.1: sheep_verify_tree*, sheep_tree_facts_dev; 1.2: sheep_read_net_dev, sheep_records_load_net
+int sheep_abi_version(void) { return (1 << 16) | 2; }
 
 const char* sheep_last_error(void) { return g_last_error.c_str(); }
 
@@ -1990,7 +1999,7 @@ int sheep_set_option(const char* name, long long value) {
   Knobs& k = knobs();
   for (const KnobDef& d : kKnobs)
     if (!strcmp(d.name, name)) {
-      k.*d.field = (int)value;
+      k.*d.field = knob_value(d, value);
       return SHEEP_OK;
     }
   throw ApiError(-EINVAL, std::string("unknown option ") + name);
@@ -2497,6 +2506,185 @@ int sheep_read_dat_dev(const char* path, uint64_t part, uint64_t num_parts, uint
   if (!d_uv) return SHEEP_OK;  // size query
   if (cap < m) throw ApiError(-ERANGE, "d_uv holds fewer records than the range");
   const uint32_t mx = ingest_dat(c, f.get(), lo, m, d_uv, nullptr, pick(c, stream));
+  if (max_id_out) *max_id_out = mx;
+  API_END
+}
+
+// ---- SNAP text (.net) ingest (net_layout.h has the semantics; sheep_ingest.hip the kernels) ----
+
+// The argument errors of a .net call, answered before any device is touched.  Returns the file.
+static FILE* open_net(const char* path, uint64_t part, uint64_t num_parts) {
+  if (!path) throw ApiError(-EINVAL, "null path");
+  if (num_parts && (part < 1 || part > num_parts))
+    throw ApiError(-EINVAL, "part must be in [1, num_parts]");
+  FILE* f = fopen(path, "rb");
+  if (!f) throw ApiError(-ENOENT, std::string("cannot open ") + path);
+  return f;
+}
+
+// The staging of a .net call: two pinned and two device text buffers of one chunk each (+ 32:
+// the final '\n', and the last word's 16-byte load) and the events that mark a buffer's upload
+// done.  One set serves the count pass and the storing pass.
+struct NetBufs {
+  uint64_t chunk;
+  uint8_t* pin[2] = {nullptr, nullptr};
+  uint8_t* txt[2] = {nullptr, nullptr};
+  hipEvent_t done[2] = {nullptr, nullptr};
+  explicit NetBufs(uint64_t chunk_) : chunk(chunk_) {
+    try {
+      for (int i = 0; i < 2; ++i) {
+        HIP_CHECK(hipHostMalloc((void**)&pin[i], chunk + 32, hipHostMallocDefault));
+        HIP_CHECK(hipMalloc(&txt[i], chunk + 32));
+        HIP_CHECK(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
+      }
+    } catch (...) {
+      release();
+      throw;
+    }
+  }
+  NetBufs(const NetBufs&) = delete;
+  NetBufs& operator=(const NetBufs&) = delete;
+  ~NetBufs() { release(); }
+  void release() {
+    for (int i = 0; i < 2; ++i) {
+      if (pin[i]) (void)hipHostFree(pin[i]);
+      if (txt[i]) (void)hipFree(txt[i]);
+      if (done[i]) (void)hipEventDestroy(done[i]);
+      pin[i] = txt[i] = nullptr;
+      done[i] = nullptr;
+    }
+  }
+};
+
+// One pass over the text of f (net_feed, net_layout.h): chunk k+1 is read while chunk k uploads
+// and is parsed; the host waits only to reuse a buffer.  dev null: the count pass; else the
+// tokens of [lo2, hi2) are stored at dev[t - lo2].  Leaves the pass's words in h (NET_WORDS u64)
+// and returns the file offset of a token that does not end within one chunk (NET_NONE: none; the
+// pass stops there).  Synchronises s, also when it throws (the buffers may then be freed).
+static uint64_t net_pass(Ctx& c, FILE* f, NetBufs& B, uint32_t* dev, uint64_t lo2, uint64_t hi2,
+                         unsigned long long* h, hipStream_t s) {
+  uint64_t long_token = NET_NONE;
+  try {
+    uint32_t* tiles = (uint32_t*)c.scratch.get("net_tiles", (size_t)net_tiles(B.chunk + 32) * 4);
+    unsigned long long* state = (unsigned long long*)c.scratch.get("net_state", NET_WORDS * 8);
+    HIP_CHECK(hipMemsetAsync(state, 0, NET_WORDS * 8, s));
+    HIP_CHECK(hipMemsetAsync(state + NET_STOP_TOK, 0xFF, 16, s));
+    if (fseeko(f, 0, SEEK_SET) != 0) throw ApiError(-EIO, "seek");
+    long_token = net_feed(
+        B.pin, B.chunk,
+        [&](uint8_t* dst, uint64_t want) -> uint64_t {
+          const size_t got = fread(dst, 1, want, f);
+          if (got < want && ferror(f)) throw ApiError(-EIO, "read");
+          return got;
+        },
+        [&](int i) { HIP_CHECK(hipEventSynchronize(B.done[i])); },  // chunk k-2's upload is done
+        [&](int i, uint64_t cut, uint64_t off) {
+          HIP_CHECK(hipMemcpyAsync(B.txt[i], B.pin[i], cut, hipMemcpyHostToDevice, s));
+          launch_net_chunk(B.txt[i], (uint32_t)cut, off, tiles, state, dev, lo2, hi2, s);
+          HIP_CHECK(hipEventRecord(B.done[i], s));
+        });
+    unsigned long long* hp = (unsigned long long*)c.h_pinned;
+    HIP_CHECK(hipMemcpyAsync(hp, state, 5 * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    for (int i = 0; i < 5; ++i) h[i] = hp[i];
+  } catch (...) {
+    (void)hipStreamSynchronize(s);
+    throw;
+  }
+  return long_token;
+}
+
+// What the count pass of a .net file finds: the device's tokens end at t_dev, the first irregular
+// token (or the file's end); from that token's first byte the host has run the reference's own
+// extraction, whose values (tail) continue the token sequence; [lo, hi) are the records of
+// part/num_parts among the R = (t_dev + tail.size()) / 2 of the file.
+struct NetPlan {
+  uint64_t t_dev = 0, lo = 0, hi = 0;
+  std::vector<uint32_t> tail;
+};
+
+static NetPlan net_plan(Ctx& c, FILE* f, NetBufs& B, const char* path, uint64_t part,
+                        uint64_t num_parts, hipStream_t s) {
+  NetPlan P;
+  unsigned long long h[NET_WORDS];
+  const uint64_t long_token = net_pass(c, f, B, nullptr, 0, 0, h, s);
+  P.t_dev = std::min<uint64_t>(h[NET_TOTAL], h[NET_STOP_TOK]);
+  const uint64_t tail_at = h[NET_STOP_TOK] != NET_NONE ? (uint64_t)h[NET_STOP_OFF] : long_token;
+  if (tail_at != NET_NONE) {
+    std::ifstream in(path);
+    in.seekg((std::streamoff)tail_at);
+    unsigned v;
+    while (in >> v) P.tail.push_back(v);
+  }
+  net_range((P.t_dev + P.tail.size()) / 2, part, num_parts, &P.lo, &P.hi);
+  return P;
+}
+
+// The storing pass: the records [P.lo, P.hi) into dev (and host, nullable), the tail's values
+// behind the device's.  Returns max id + 1.  Synchronises s.
+static uint32_t net_store(Ctx& c, FILE* f, NetBufs& B, const NetPlan& P, uint32_t* dev,
+                          uint32_t* host, hipStream_t s) {
+  const uint64_t lo2 = 2 * P.lo, hi2 = 2 * P.hi, m = P.hi - P.lo;
+  uint32_t mx = 0;
+  if (std::min(hi2, P.t_dev) > lo2) {
+    unsigned long long h[NET_WORDS];
+    net_pass(c, f, B, dev, lo2, std::min(hi2, P.t_dev), h, s);
+    mx = (uint32_t)h[NET_MAX];
+  }
+  const uint64_t a = std::max(lo2, P.t_dev);  // the tail's tokens inside the window: [a, hi2)
+  if (a < hi2) {
+    const uint32_t* src = P.tail.data() + (a - P.t_dev);
+    for (uint64_t i = 0; i < hi2 - a; ++i) mx = std::max(mx, net_top(src[i]));
+    HIP_CHECK(hipMemcpyAsync(dev + (a - lo2), src, (hi2 - a) * 4, hipMemcpyHostToDevice, s));
+  }
+  if (host && m) HIP_CHECK(hipMemcpyAsync(host, dev, 8 * m, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (mx == INV)  // max id + 1 does not fit u32: a record names INVALID (or 0xFFFFFFFE)
+    throw ApiError(-ERANGE, "a record's vertex id is 0xFFFFFFFE or 0xFFFFFFFF (u32 id space)");
+  return mx;
+}
+
+int sheep_records_load_net(const char* path, uint64_t part, uint64_t num_parts, uint32_t* uv_out,
+                           uint64_t cap, uint64_t* m_out, uint32_t* max_id_out) {
+  API_BEGIN
+  std::unique_ptr<FILE, int (*)(FILE*)> f(open_net(path, part, num_parts), fclose);
+  Ctx& c = ctx();
+  for (const Ctx::Registered& r : c.registered)
+    if (uv_out && r.host == uv_out) throw ApiError(-EBUSY, "records already registered");
+  NetBufs B(net_chunk_clamp(knobs().net_chunk));
+  const NetPlan P = net_plan(c, f.get(), B, path, part, num_parts, c.stream);
+  const uint64_t m = P.hi - P.lo;
+  if (m_out) *m_out = m;
+  if (!uv_out) return SHEEP_OK;  // size query
+  require_records(m, "net ingest");
+  if (cap < m) throw ApiError(-ERANGE, "uv_out holds fewer records than the range");
+  uint32_t* dev = nullptr;
+  HIP_CHECK(hipMalloc(&dev, std::max<uint64_t>(8 * m, 8)));
+  try {
+    const uint32_t mx = net_store(c, f.get(), B, P, dev, uv_out, c.stream);
+    if (max_id_out) *max_id_out = mx;
+  } catch (...) {
+    (void)hipFree(dev);
+    throw;
+  }
+  c.registered.push_back({uv_out, m, dev});
+  API_END
+}
+
+int sheep_read_net_dev(const char* path, uint64_t part, uint64_t num_parts, uint32_t* d_uv,
+                       uint64_t cap, uint64_t* m_out, uint32_t* max_id_out, void* stream) {
+  API_BEGIN
+  std::unique_ptr<FILE, int (*)(FILE*)> f(open_net(path, part, num_parts), fclose);
+  Ctx& c = ctx();
+  hipStream_t s = pick(c, stream);
+  NetBufs B(net_chunk_clamp(knobs().net_chunk));
+  const NetPlan P = net_plan(c, f.get(), B, path, part, num_parts, s);
+  const uint64_t m = P.hi - P.lo;
+  if (m_out) *m_out = m;
+  if (!d_uv) return SHEEP_OK;  // size query
+  require_records(m, "net ingest");
+  if (cap < m) throw ApiError(-ERANGE, "d_uv holds fewer records than the range");
+  const uint32_t mx = net_store(c, f.get(), B, P, d_uv, nullptr, s);
   if (max_id_out) *max_id_out = mx;
   API_END
 }

@@ -70,6 +70,8 @@ struct Knobs {
                          //   pre-bucket roots (CAS INVALID -> b), leaving the rest to the zipper
   int eval_pass = 31;    // SHEEP_EVAL_PASS: at most 2^eval_pass adjacency entries sorted per pass
                          //   of the partition evaluation (more: passes over id ranges)
+  int net_chunk = 32 << 20;  // SHEEP_NET_CHUNK: bytes of text per chunk of the .net ingest, kept
+                         //   in [4096, 2^30] and a multiple of 16 (net_layout.h net_chunk_clamp)
 };
 Knobs& knobs();  // the process-wide options (sheep_capi.cpp)
 
@@ -422,6 +424,13 @@ void launch_vf_facts(const VfTour& T, const uint32_t* pst, long long* wv, long l
                      long long* sums, unsigned long long* ws, hipStream_t s);
 // XS1 records {u32 tail, u32 head, f32 weight} -> (tail, head) pairs; max id + 1 into *max_id.
 void launch_strip_xs1(const uint32_t* raw, uint64_t n, uint32_t* uv, uint32_t* max_id, hipStream_t s);
+// One chunk of SNAP text (sheep_ingest.hip; net_layout.h): n bytes at text (allocated up to a
+// multiple of 16), the chunk's first byte at file_off; tiles: net_tiles(n) u32 scratch; state:
+// the pass's NET_WORDS u64.  uv null: the count pass (token count and stop pair only); else the
+// values of the tokens in [lo2, hi2) go to uv[t - lo2] and their max id + 1 to NET_MAX.
+void launch_net_chunk(const uint8_t* text, uint32_t n, uint64_t file_off, uint32_t* tiles,
+                      unsigned long long* state, uint32_t* uv, uint64_t lo2, uint64_t hi2,
+                      hipStream_t s);
 void launch_merge(uint32_t* parent_a, uint32_t* pst_a, const uint32_t* parent_b,
                   const uint32_t* pst_b, uint32_t n, uint32_t* jump, hipStream_t s);
 void launch_rmat(uint32_t* uv, int scale, uint64_t seed, uint64_t e_begin, uint64_t e_end,

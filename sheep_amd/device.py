@@ -285,3 +285,17 @@ def read_dat(path, part=0, num_parts=0, device="cuda"):
     capi.call("sheep_read_dat_dev", str(path).encode(), part, num_parts, _p(uv), m.value,
               ctypes.byref(m), ctypes.byref(mx), _stream())
     return uv[:m.value], mx.value
+
+
+def read_net(path, part=0, num_parts=0, device="cuda"):
+    """Records of a SNAP text (.net) file (or the part/num_parts range, 1-based as graph2tree -l),
+    tokenised and converted on the GPU, the stream SNAPReader yields: (uv (m, 2) uint32 tensor,
+    max id + 1).  The size query is a count pass over the file."""
+    m = ctypes.c_uint64(0)
+    capi.call("sheep_read_net_dev", str(path).encode(), part, num_parts, None, 0, ctypes.byref(m),
+              None, _stream())
+    uv = torch.empty((max(m.value, 1), 2), dtype=torch.uint32, device=device)
+    mx = ctypes.c_uint32(0)
+    capi.call("sheep_read_net_dev", str(path).encode(), part, num_parts, _p(uv), m.value,
+              ctypes.byref(m), ctypes.byref(mx), _stream())
+    return uv[:m.value], mx.value

@@ -3,7 +3,8 @@
 // LLAMA is not part of this build: the graph is the edge stream itself, held as u32 (tail,
 // head) pairs (what the GPU consumes), with a lazily built undirected-double CSR for the
 // host-side iterators (partition evaluation / partitioned output).  Semantics kept:
-//   - .dat loads every complete record (no XS1Reader tail duplication), .net via SNAPReader;
+//   - .dat loads every complete record (no XS1Reader tail duplication), .net via SNAPReader
+//     (loaded to_device: the same stream, parsed on the GPU);
 //   - undirected double: record (t,h) is adjacency t->h and h->t, a self-loop is stored once;
 //   - duplicates are kept (no DDUP_GRAPH);
 //   - partial load part/num_parts (1-based part, graph2tree -l) takes the contiguous record
@@ -56,19 +57,21 @@ class EdgeGraph {
     if (reg_) (void)sheep_records_release(reg_);
   }
 
-  // to_device: a .dat file goes straight to HBM through pinned staging (sheep_records_load_dat)
-  // and stays there for every GPU call on this graph; the host copy is filled on the way.
+  // to_device: the file goes straight to HBM through pinned staging (a .dat file's records by
+  // sheep_records_load_dat; any other file is SNAP text, tokenised and converted on the device
+  // by sheep_records_load_net, SNAPReader's stream) and stays there for every GPU call on this
+  // graph; the host copy is filled on the way.
   EdgeGraph(char const* filename, size_t part, size_t num_parts, bool to_device) {
-    if (!to_device || !is_dat(filename)) {
+    if (!to_device) {
       *this = EdgeGraph(filename, part, num_parts);
-      if (to_device) this->to_device();
       return;
     }
+    auto load = is_dat(filename) ? sheep_records_load_dat : sheep_records_load_net;
     uint64_t m = 0;
     uint32_t mx = 0;
-    sheep_check(sheep_records_load_dat(filename, part, num_parts, nullptr, 0, &m, nullptr), "load");
+    sheep_check(load(filename, part, num_parts, nullptr, 0, &m, nullptr), "load");
     uv_.resize(2 * std::max<uint64_t>(m, 1));
-    sheep_check(sheep_records_load_dat(filename, part, num_parts, uv_.data(), m, &m, &mx), "load");
+    sheep_check(load(filename, part, num_parts, uv_.data(), m, &m, &mx), "load");
     uv_.resize(2 * m);
     reg_ = uv_.data();
     max_vid_ = mx;
