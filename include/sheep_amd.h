@@ -31,7 +31,9 @@
  *
  * ABI 1.1 adds sheep_verify_tree_dev, sheep_verify_tree and sheep_tree_facts_dev; nothing else
  * changed.  ABI 1.2 adds sheep_read_net_dev and sheep_records_load_net (SNAP text parsed on the
- * device) and the option net_chunk; nothing else changed.
+ * device) and the option net_chunk; nothing else changed.  ABI 1.3 adds sheep_tree_widths_dev
+ * and sheep_tree_widths (the exact width of every bag, without storing a bag); nothing else
+ * changed.
  */
 #ifndef SHEEP_AMD_H
 #define SHEEP_AMD_H
@@ -362,6 +364,29 @@ int sheep_verify_tree(const uint32_t* edges_uv, uint64_t m, const uint32_t* seq,
  * forest that is not in heap order.  Synchronises the stream. */
 int sheep_tree_facts_dev(const uint32_t* d_parent, const uint32_t* d_pst, uint32_t n,
                          uint64_t* out, void* stream);
+/* The exact widths of a tree built over the records: width[j] = 1 + |jxn(j)|, what the
+ * reference's graph2tree -k -e -j stores bag by bag (jtree.cpp:66-110, jnode.h:230-255), from
+ * subtree sums in Euler-tour order; no bag is materialised and the work does not depend on the
+ * tree's height or fan-out.  A record with one end outside the sequence keeps that id in every
+ * bag from its inside end up to the root; a record with both ends outside counts nothing.
+ * d_width (n_seq words, nullable): the width of every jnid.  out (host, 9 words) in TREEFAQS
+ * order as sheep_tree_facts_dev: roots, vheight, eheight, verts and edges are that call's; width
+ * = max width[j]; fill = the sum of width[j] - 1 - pst[j] modulo 2^64 (the reference's size_t
+ * sum); halo = the first jnid with width > 3; core = 0.
+ * The tree must be an elimination tree of these records at least as far as property (A) of
+ * sheep_verify_tree_dev: -EINVAL, naming the count, if some record's upper end is no ancestor
+ * of its lower end.  -EINVAL also: a null argument, m >= 2^32 (both before any device is
+ * touched), n_seq >= 2^31, n_seq + n_ids > 2^32, a forest not in heap order; -ERANGE as
+ * sheep_build_tree_dev.  n_seq == 0: zeros, halo and core SHEEP_INVALID.  Phase times through
+ * sheep_last_timings.  Synchronises the stream. */
+int sheep_tree_widths_dev(const uint32_t* d_uv, uint64_t m, const uint32_t* d_rank, uint32_t n_ids,
+                          uint32_t n_seq, const uint32_t* d_parent, const uint32_t* d_pst,
+                          uint32_t* d_width, uint64_t* out, void* stream);
+/* The same from host arrays (width_out nullable): uploads them (or uses the registered device
+ * copy of (edges_uv, m)) and builds the rank map from seq, as sheep_verify_tree. */
+int sheep_tree_widths(const uint32_t* edges_uv, uint64_t m, const uint32_t* seq, uint32_t n_seq,
+                      const uint32_t* parent, const uint32_t* pst, uint32_t* width_out,
+                      uint64_t* out);
 
 /* The whole single-device hot path: degree -> sequence -> tree (graph2tree's Sorted+Mapped).
  * d_seq holds n_ids entries, d_parent/d_pst hold n_ids entries (n_seq used).  Synchronises. */

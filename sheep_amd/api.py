@@ -201,6 +201,21 @@ def tree_facts(tree):
     return device.tree_facts(parent, pst)
 
 
+def tree_widths(uv, seq, tree):
+    """The exact width 1 + |jxn| of every node of ``tree`` built over the records under ``seq``,
+    on the GPU and without storing a bag (sheep_tree_widths; what graph2tree -k -e -j reports).
+    Returns (numpy uint32 widths, TREEFAQS dict with the true width, fill and halo)."""
+    uv = _as_edges(uv)
+    seq = np.ascontiguousarray(seq, np.uint32)
+    if tree.size() != seq.size:
+        raise SheepError(-errno.EINVAL, "tree_widths: tree and sequence of different sizes")
+    out = np.zeros(9, np.uint64)
+    width = np.zeros(seq.size, np.uint32)
+    capi.call("sheep_tree_widths", _ptr(uv), uv.shape[0], _ptr(seq), seq.size, _ptr(tree.parent),
+              _ptr(tree.pst), _ptr(width), _ptr(out))
+    return width, dict(zip(capi.FACT_KEYS, (int(x) for x in out)))
+
+
 def graph2tree(uv, mode=DEGREE_LLAMA):
     """graph2tree's serial path (graph2tree.cpp:162-193): degreeSequence + JTree."""
     seq = degree_sequence(uv, mode)

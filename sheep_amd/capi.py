@@ -112,6 +112,9 @@ def lib():
                                   vp],
         "sheep_verify_tree": [u32p, c.c_uint64, u32p, c.c_uint32, u32p, u32p, vp],
         "sheep_tree_facts_dev": [u32p, u32p, c.c_uint32, vp, vp],
+        "sheep_tree_widths_dev": [u32p, c.c_uint64, u32p, c.c_uint32, c.c_uint32, u32p, u32p, u32p,
+                                  vp, vp],
+        "sheep_tree_widths": [u32p, c.c_uint64, u32p, c.c_uint32, u32p, u32p, u32p, vp],
         "sheep_partition": [u32p, u32p, c.c_uint32, u32p, vp, c.c_uint32, c.c_double, vp,
                             c.c_uint32, vp],
     }
@@ -151,6 +154,8 @@ def set_option(name, value):
     return old.value
 
 
+# the 9 words of sheep_tree_facts_dev / sheep_tree_widths*, in TREEFAQS print order
+FACT_KEYS = ("width", "roots", "vheight", "eheight", "verts", "edges", "halo", "core", "fill")
 REPORT_KEYS = ("heap", "ancestor", "witness", "pst", "first")
 NOT_COMPUTED = 0xFFFFFFFFFFFFFFFF
 

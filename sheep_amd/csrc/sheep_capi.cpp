@@ -25,6 +25,7 @@
 #include "sheep_internal.h"
 #include "net_layout.h"
 #include "verify_layout.h"
+#include "width_layout.h"
 
 namespace sheep {
 
@@ -1972,8 +1973,9 @@ static void require_aligned(const void* p, const char* what) {
 
 extern "C" {
 
-// 1.1: sheep_verify_tree*, sheep_tree_facts_dev; 1.2: sheep_read_net_dev, sheep_records_load_net
-int sheep_abi_version(void) { return (1 << 16) | 2; }
+// 1.1: sheep_verify_tree*, sheep_tree_facts_dev; 1.2: sheep_read_net_dev, sheep_records_load_net;
+// 1.3: sheep_tree_widths*
+int sheep_abi_version(void) { return (1 << 16) | 3; }
 
 const char* sheep_last_error(void) { return g_last_error.c_str(); }
 
@@ -2343,6 +2345,97 @@ static void tree_facts_dev(Ctx& c, const uint32_t* d_parent, const uint32_t* d_p
   out[6] = (uint32_t)h[VF_HALO];
   out[7] = 0;
   out[8] = 0;
+}
+
+// ---- exact tree widths (sheep_width.hip) ---------------------------------------------------
+
+static void tree_widths_dev(Ctx& c, const uint32_t* d_uv, uint64_t m, const uint32_t* d_rank,
+                            uint32_t n_ids, uint32_t n_seq, const uint32_t* d_parent,
+                            const uint32_t* d_pst, uint32_t* d_width, uint64_t* out, hipStream_t s) {
+  for (int i = 0; i < 9; ++i) out[i] = 0;
+  out[6] = out[7] = INV;  // halo, core: none
+  if (n_seq == 0) return;
+  // an id outside the sequence sorts as the upper end n_seq + id (width_layout.h tw_outside_key)
+  if ((uint64_t)n_seq + n_ids > (1ull << 32))
+    throw ApiError(-EINVAL, "tree widths: n_seq + n_ids above 2^32 (u32 sort keys)");
+  Scratch& sc = c.scratch;
+  Timer tm(s);
+  unsigned long long* vws;
+  std::vector<unsigned long long> h = vf_heap(c, d_parent, n_seq, &vws, s);
+  tm.mark("vf_heap");
+  if (h[VF_HEAP]) throw ApiError(-EINVAL, "tree widths: forest not heap-ordered");
+  const VfTour T = vf_tour(c, d_parent, n_seq, s);
+  tm.mark("vf_tour");
+  long long* sums = (long long*)sc.get("vf_scan_sums", vf_scan_tiles(n_seq) * 8);
+  long long* sv = (long long*)T.cells_a;  // the depths; T.cells_b is free again after the facts
+  launch_vf_facts(T, d_pst, sv, (long long*)T.cells_b, sums, vws, s);
+  tm.mark("vf_facts");
+
+  const size_t n2 = 2 * (size_t)n_seq;
+  const uint32_t nb = tw_blocks(n2);
+  TwBufs B;
+  B.depth = (uint32_t*)sc.get("tw_depth", n2 * 4);
+  B.pre = (uint64_t*)sc.get("tw_pre", n2 * 8);
+  B.suf = (uint64_t*)sc.get("tw_suf", n2 * 8);
+  B.tab = (uint64_t*)sc.get("tw_tab", (size_t)tw_levels(nb) * nb * 8);
+  B.lca_tin = (uint32_t*)sc.get("tw_lca_tin", n2 * 4);
+  B.has_lower = (uint8_t*)sc.get("tw_has_lower", n_seq);
+  unsigned long long* ws = (unsigned long long*)sc.get("tw_ws", TW_WS_WORDS * 8);
+  launch_tw_rmq(T, d_parent, sv, B, ws, s);
+  tm.mark("tw_rmq");
+
+  const uint64_t* sorted = nullptr;
+  if (m) {
+    uint64_t* keys = (uint64_t*)sc.get("tw_keys", m * 8);
+    uint64_t* keys_b = (uint64_t*)sc.get("tw_keys_b", m * 8);
+    uint32_t* rtmp = (uint32_t*)sc.get("tw_rsort_tmp", rsort_tmp_words(m) * 4);
+    launch_tw_keys(d_uv, m, d_rank, n_ids, T, keys, ws, c.d_err, s);
+    tm.mark("tw_keys");
+    // LSD: the tin bits of the lower word (radix_sort_u64 counts bits from the upper word's
+    // bit 0), then the upper ends; TW_SKIP has every bit set and stays last
+    uint64_t* r = radix_sort_u64(keys, keys_b, keys, m, -32, -32 + bits_for(n2 - 1), rtmp, s);
+    uint64_t* o = r == keys ? keys_b : keys;
+    sorted = radix_sort_u64(r, o, r, m, 0, bits_for((uint64_t)n_seq + n_ids - 1), rtmp, s);
+    tm.mark("tw_sort");
+  }
+  long long* wt = (long long*)T.cells_b;
+  launch_tw_weights(sorted, m, T, B, wt, s);
+  tm.mark("tw_weights");
+  launch_vf_scan(wt, n_seq, sums, s);
+  launch_tw_final(T, d_pst, wt, d_width, ws, s);
+  tm.mark("tw_scan");
+  h = vf_read_ws(vws, s);
+  std::vector<unsigned long long> w(TW_WS_WORDS);
+  HIP_CHECK(hipMemcpyAsync(w.data(), ws, TW_WS_WORDS * 8, hipMemcpyDeviceToHost, s));
+  check_err(c, s);  // synchronises; -ERANGE as the tree build
+  tm.finish(c);
+  if (w[TW_A])
+    throw ApiError(-EINVAL, "tree widths: " + std::to_string(w[TW_A]) +
+                                " records whose upper end is no ancestor of the lower end");
+  // TREEFAQS print order, as tree_facts_dev.  core: the first id whose width reaches the running
+  // maximum, which already includes that id, is id 0.
+  out[0] = w[TW_WIDTH];
+  out[1] = h[VF_ROOTS];
+  out[2] = h[VF_VH];
+  out[3] = h[VF_EH];
+  out[4] = n_seq;
+  out[5] = h[VF_EDGES];
+  out[6] = (uint32_t)w[TW_HALO];
+  out[7] = 0;
+  out[8] = w[TW_FILL];
+}
+
+int sheep_tree_widths_dev(const uint32_t* d_uv, uint64_t m, const uint32_t* d_rank, uint32_t n_ids,
+                          uint32_t n_seq, const uint32_t* d_parent, const uint32_t* d_pst,
+                          uint32_t* d_width, uint64_t* out, void* stream) {
+  API_BEGIN
+  if (!out || (m && !d_uv) || (n_ids && !d_rank) || (n_seq && (!d_parent || !d_pst)))
+    throw ApiError(-EINVAL, "sheep_tree_widths_dev: null argument");
+  require_records(m, "tree widths");
+  Ctx& c = ctx();
+  require_aligned(d_uv, "d_uv");
+  tree_widths_dev(c, d_uv, m, d_rank, n_ids, n_seq, d_parent, d_pst, d_width, out, pick(c, stream));
+  API_END
 }
 
 int sheep_verify_tree_dev(const uint32_t* d_uv, uint64_t m, const uint32_t* d_rank, uint32_t n_ids,
@@ -3183,6 +3276,40 @@ int sheep_verify_tree(const uint32_t* edges_uv, uint64_t m, const uint32_t* seq,
     HIP_CHECK(hipMemcpyAsync(dpst, pst, nb, hipMemcpyHostToDevice, s));
   }
   verify_tree_dev(c, uv, m, rank, n_rank, n_seq, dparent, dpst, report, s);
+  API_END
+}
+
+int sheep_tree_widths(const uint32_t* edges_uv, uint64_t m, const uint32_t* seq, uint32_t n_seq,
+                      const uint32_t* parent, const uint32_t* pst, uint32_t* width_out,
+                      uint64_t* out) {
+  API_BEGIN
+  if (!out || (m && !edges_uv) || (n_seq && (!seq || !parent || !pst)))
+    throw ApiError(-EINVAL, "sheep_tree_widths: null argument");
+  require_records(m, "tree widths");
+  for (int i = 0; i < 9; ++i) out[i] = 0;
+  out[6] = out[7] = INV;
+  if (n_seq == 0) return SHEEP_OK;
+  Ctx& c = ctx();
+  hipStream_t s = c.stream;
+  const size_t nb = (size_t)n_seq * 4;
+  uint32_t n_rank = *std::max_element(seq, seq + n_seq) + 1;  // as sheep_build_tree
+  uint32_t* uv = upload_records(c, edges_uv, m, s);
+  uint32_t* dseq = (uint32_t*)c.scratch.get("h_seq", nb);
+  HIP_CHECK(hipMemcpyAsync(dseq, seq, nb, hipMemcpyHostToDevice, s));
+  uint32_t* rank = (uint32_t*)c.scratch.get("rank", (size_t)n_rank * 4);
+  launch_fill(rank, INV, n_rank, s);
+  launch_rank_scatter(dseq, n_seq, rank, c.d_err, s);
+  check_err(c, s);
+  uint32_t* dparent = (uint32_t*)c.scratch.get("h_parent", nb);
+  HIP_CHECK(hipMemcpyAsync(dparent, parent, nb, hipMemcpyHostToDevice, s));
+  uint32_t* dpst = (uint32_t*)c.scratch.get("h_pst", nb);
+  HIP_CHECK(hipMemcpyAsync(dpst, pst, nb, hipMemcpyHostToDevice, s));
+  uint32_t* dwidth = width_out ? (uint32_t*)c.scratch.get("h_width", nb) : nullptr;
+  tree_widths_dev(c, uv, m, rank, n_rank, n_seq, dparent, dpst, dwidth, out, s);
+  if (width_out) {
+    HIP_CHECK(hipMemcpyAsync(width_out, dwidth, nb, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
   API_END
 }
 

@@ -404,6 +404,19 @@ struct VfTour {
   uint2* tt = nullptr;          // n: (tin, tout) tour positions per rank
   uint32_t* ktin = nullptr;     // n: tin of the child in each slot
 };
+// Wave reductions of the verifier's and the widths' counters (the result in lane 0).
+__device__ __forceinline__ unsigned long long vf_wave_sum(unsigned long long c) {
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+  return c;
+}
+__device__ __forceinline__ uint32_t vf_wave_min(uint32_t c) {
+  for (int o = 32; o > 0; o >>= 1) c = min(c, (uint32_t)__shfl_down(c, o));
+  return c;
+}
+__device__ __forceinline__ unsigned long long vf_wave_max(unsigned long long c) {
+  for (int o = 32; o > 0; o >>= 1) c = max(c, (unsigned long long)__shfl_down(c, o));
+  return c;
+}
 // Resets ws, then counts heap-order violations (VF_HEAP, VF_MIN) and roots (VF_ROOTS).
 void launch_vf_heap(const uint32_t* parent, uint32_t n, unsigned long long* ws, hipStream_t s);
 void launch_vf_items(const uint32_t* parent, uint32_t n, uint64_t* items, hipStream_t s);
@@ -422,6 +435,33 @@ void launch_vf_final(const uint32_t* parent, const uint32_t* pst, const uint32_t
 size_t vf_scan_tiles(uint32_t n);
 void launch_vf_facts(const VfTour& T, const uint32_t* pst, long long* wv, long long* we,
                      long long* sums, unsigned long long* ws, hipStream_t s);
+// In-place inclusive scan of the 2n i64 values of a tour (sums: vf_scan_tiles(n) i64).
+void launch_vf_scan(long long* io, uint32_t n, long long* sums, hipStream_t s);
+// Exact tree widths (sheep_width.hip; index arithmetic in width_layout.h).  The counter words
+// (ws: TW_WS_WORDS u64, reset by launch_tw_rmq): records violating (A), then the reductions.
+enum { TW_A = 0, TW_WIDTH, TW_FILL, TW_HALO, TW_WS_WORDS = 8 };
+struct TwBufs {
+  uint32_t* depth = nullptr;    // 2n: depth after the arc at each tour position
+  uint64_t* pre = nullptr;      // 2n each: in-block prefix / suffix minima (depth << 32 | pos)
+  uint64_t* suf = nullptr;
+  uint64_t* tab = nullptr;      // tw_levels(nb) * nb: the sparse table over the block minima
+  uint32_t* lca_tin = nullptr;  // 2n: tin of the rank a minimum at this position names (INV: none)
+  uint8_t* has_lower = nullptr;  // n: the rank is some record's upper end
+};
+// The range-minimum structure from the depths sv (launch_vf_facts's first scan) of a toured forest.
+void launch_tw_rmq(const VfTour& T, const uint32_t* parent, const long long* sv, const TwBufs& B,
+                   unsigned long long* ws, hipStream_t s);
+// keys[i] (m u64) of every record: (hi << 32 | tin lo), TW_SKIP for one that counts nothing;
+// (A) violations into ws[TW_A]; ERR_RANGE as launch_vf_records.
+void launch_tw_keys(const uint32_t* uv, uint64_t m, const uint32_t* rank, uint32_t n_ids,
+                    const VfTour& T, uint64_t* keys, unsigned long long* ws, uint32_t* err,
+                    hipStream_t s);
+// From the sorted keys: the weights wt (2n i64, zeroed here) at tin positions.
+void launch_tw_weights(const uint64_t* keys, uint64_t m, const VfTour& T, const TwBufs& B,
+                       long long* wt, hipStream_t s);
+// From the scanned weights S: width_out (n, nullable), ws[TW_WIDTH .. TW_HALO].
+void launch_tw_final(const VfTour& T, const uint32_t* pst, const long long* S, uint32_t* width_out,
+                     unsigned long long* ws, hipStream_t s);
 // XS1 records {u32 tail, u32 head, f32 weight} -> (tail, head) pairs; max id + 1 into *max_id.
 void launch_strip_xs1(const uint32_t* raw, uint64_t n, uint32_t* uv, uint32_t* max_id, hipStream_t s);
 // One chunk of SNAP text (sheep_ingest.hip; net_layout.h): n bytes at text (allocated up to a

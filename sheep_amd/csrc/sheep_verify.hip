@@ -41,18 +41,6 @@ static inline unsigned vf_grid(uint64_t n) {
   return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(g, 4096));
 }
 
-__device__ __forceinline__ unsigned long long vf_wave_sum(unsigned long long c) {
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-  return c;
-}
-__device__ __forceinline__ uint32_t vf_wave_min(uint32_t c) {
-  for (int o = 32; o > 0; o >>= 1) c = min(c, (uint32_t)__shfl_down(c, o));
-  return c;
-}
-__device__ __forceinline__ unsigned long long vf_wave_max(unsigned long long c) {
-  for (int o = 32; o > 0; o >>= 1) c = max(c, (unsigned long long)__shfl_down(c, o));
-  return c;
-}
 // The low word of a counter word holds a rank minimum (little endian; the high word stays 0).
 __device__ __forceinline__ void vf_min_rank(unsigned long long* w, uint32_t v) {
   if (v != INV) atomicMin((uint32_t*)w, v);
@@ -394,20 +382,23 @@ void launch_vf_final(const uint32_t* parent, const uint32_t* pst, const uint32_t
 
 size_t vf_scan_tiles(uint32_t n) { return (size_t)((2ull * n + VF_SCAN_TILE - 1) / VF_SCAN_TILE); }
 
+void launch_vf_scan(long long* io, uint32_t n, long long* sums, hipStream_t s) {
+  if (n == 0) return;
+  const uint64_t n2 = 2ull * n, nt = vf_scan_tiles(n);
+  hipLaunchKernelGGL(k_vf_scan_sums, dim3((unsigned)nt), dim3(VF_SCAN_T), 0, s, (const long long*)io,
+                     n2, sums);
+  hipLaunchKernelGGL(k_vf_scan_top, dim3(1), dim3(VF_SCAN_T), 0, s, sums, nt);
+  hipLaunchKernelGGL(k_vf_scan_apply, dim3((unsigned)nt), dim3(VF_SCAN_T), 0, s, io, n2,
+                     (const long long*)sums);
+}
+
 void launch_vf_facts(const VfTour& T, const uint32_t* pst, long long* wv, long long* we,
                      long long* sums, unsigned long long* ws, hipStream_t s) {
   const uint32_t n = T.n;
   if (n == 0) return;
-  const uint64_t n2 = 2ull * n, nt = vf_scan_tiles(n);
   hipLaunchKernelGGL(k_vf_weights, dim3(vf_grid(n)), dim3(VF_BLOCK), 0, s, (const uint2*)T.tt, pst, n,
                      wv, we);
-  for (long long* w : {wv, we}) {
-    hipLaunchKernelGGL(k_vf_scan_sums, dim3((unsigned)nt), dim3(VF_SCAN_T), 0, s, (const long long*)w,
-                       n2, sums);
-    hipLaunchKernelGGL(k_vf_scan_top, dim3(1), dim3(VF_SCAN_T), 0, s, sums, nt);
-    hipLaunchKernelGGL(k_vf_scan_apply, dim3((unsigned)nt), dim3(VF_SCAN_T), 0, s, w, n2,
-                       (const long long*)sums);
-  }
+  for (long long* w : {wv, we}) launch_vf_scan(w, n, sums, s);
   hipLaunchKernelGGL(k_vf_facts, dim3(vf_grid(n)), dim3(VF_BLOCK), 0, s, (const uint2*)T.tt, pst, n,
                      (const long long*)wv, (const long long*)we, ws);
 }

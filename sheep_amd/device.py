@@ -190,7 +190,7 @@ def evaluate(uv, parts, rank, n_parts=None):
     return dict(zip(EVAL_KEYS, (int(x) for x in out)))
 
 
-FACT_KEYS = ("width", "roots", "vheight", "eheight", "verts", "edges", "halo", "core", "fill")
+FACT_KEYS = capi.FACT_KEYS
 report_dict = capi.report_dict
 
 
@@ -213,6 +213,20 @@ def tree_facts(parent, pst):
     capi.call("sheep_tree_facts_dev", _p(parent), _p(pst), parent.numel(),
               ctypes.c_void_p(out.ctypes.data), _stream())
     return dict(zip(FACT_KEYS, (int(x) for x in out)))
+
+
+def tree_widths(uv, rank, n_seq, parent, pst, want_widths=True):
+    """Exact bag widths of the tree (parent, pst) built over the records ``uv`` under the rank
+    map ``rank`` (sheep_tree_widths_dev): (width tensor of n_seq uint32, or None without
+    ``want_widths``; TREEFAQS dict (FACT_KEYS) with the true width, fill and halo)."""
+    import numpy as np
+
+    out = np.zeros(9, np.uint64)
+    width = torch.empty(max(n_seq, 1), dtype=torch.uint32, device=parent.device) if want_widths \
+        else None
+    capi.call("sheep_tree_widths_dev", _p(uv), uv.shape[0], _p(rank), rank.numel(), n_seq,
+              _p(parent), _p(pst), _p(width), ctypes.c_void_p(out.ctypes.data), _stream())
+    return (width[:n_seq] if want_widths else None), dict(zip(FACT_KEYS, (int(x) for x in out)))
 
 
 def graph2tree(uv, n_ids, mode=capi.DEGREE_LLAMA, seq=None, parent=None, pst=None):

@@ -39,6 +39,7 @@ class JNodeTable {
   size_t max_id_ = 0;
   std::vector<uint64_t> kid_off_;  // makeKids (jnode.h:190-204): ascending jnid order
   std::vector<jnid_t> kid_ids_;
+  std::vector<uint32_t> width_;    // 1 + |jxn| per jnid (JTree with make_jxn); empty: not computed
 
   void map_file(int fd, size_t bytes) {
     void* p = bytes ? mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0) : nullptr;
@@ -65,6 +66,7 @@ class JNodeTable {
     max_id_ = o.max_id_;
     kid_off_ = std::move(o.kid_off_);
     kid_ids_ = std::move(o.kid_ids_);
+    width_ = std::move(o.width_);
     o.map_ = nullptr;
     o.map_bytes_ = 0;
     o.nodes_ = nullptr;
@@ -138,14 +140,25 @@ class JNodeTable {
     end_id_ = (jnid_t)parent.size();
     kid_off_.clear();
     kid_ids_.clear();
+    width_.clear();
   }
+  // The exact widths of this table's nodes (sheep_tree_widths); dropped by assign, merge and
+  // mpi_merge, whose trees are other graphs'.
+  void setWidths(std::vector<uint32_t> width) {
+    if (width.size() != end_id_) throw std::invalid_argument("JNodeTable: widths of another size");
+    width_ = std::move(width);
+  }
+  bool hasWidths() const { return !width_.empty() && width_.size() == end_id_; }
 
   jnid_t size() const { return end_id_; }
   jnid_t& parent(jnid_t id) { return nodes_[id].parent; }
   jnid_t parent(jnid_t id) const { return nodes_[id].parent; }
   esize_t& pst_weight(jnid_t id) { return nodes_[id].pst_weight; }
   esize_t pst_weight(jnid_t id) const { return nodes_[id].pst_weight; }
-  size_t width(jnid_t id) const { return 1 + (size_t)nodes_[id].pst_weight; }  // jnode.h:258-260
+  // jnode.h:258-260: 1 + |jxn(id)| where the bags were asked for, else 1 + pst_weight
+  size_t width(jnid_t id) const {
+    return hasWidths() ? (size_t)width_[id] : 1 + (size_t)nodes_[id].pst_weight;
+  }
 
   std::vector<jnid_t> parents() const {
     std::vector<jnid_t> p(end_id_);

@@ -1,6 +1,8 @@
 // JTree (reference: lib/jtree.h:39-188): vid -> jnid index plus the elimination tree of the
-// graph under seq.  The tree is built on the GPU (sheep_build_tree); the chordal-extension
-// options (-k/-e/-j/-m/-w/-x) are out of scope of this build and rejected.
+// graph under seq.  The tree is built on the GPU (sheep_build_tree).  Of the chordal-extension
+// options, make_kids + make_pst + make_jxn (-k -e -j) give every node's exact width 1 + |jxn|
+// (sheep_tree_widths: computed on the GPU, no bag is stored, so memory_limit has nothing to
+// cap); a width limit, the width search and rooting (-w/-x) are out of scope and rejected.
 #pragma once
 #include <algorithm>
 #include <stdexcept>
@@ -17,16 +19,19 @@ class JTree {
  public:
   JNodeTable jnodes;
 
-  struct Options {  // jtree.h:71-108; only the default path is built here
+  struct Options {  // jtree.h:71-108
     bool verbose = false;
     bool make_pad = true;
     bool make_kids = false, make_pst = false, make_jxn = false;
     size_t memory_limit = 1 * GIGA, width_limit = (size_t)-1;
     bool find_max_width = false, do_rooting = false;
     size_t rooting_limit = 0;
+    // the bags only with the children and pst lists they are made from (the reference's
+    // Options::isValid); the lists alone have no consumer here
     bool isSupported() const {
-      return make_pad && !make_kids && !make_pst && !make_jxn && width_limit == (size_t)-1 &&
-             !find_max_width && !do_rooting && rooting_limit == 0;
+      bool const lists = make_kids || make_pst || make_jxn;
+      return make_pad && (!lists || (make_kids && make_pst && make_jxn)) &&
+             width_limit == (size_t)-1 && !find_max_width && !do_rooting && rooting_limit == 0;
     }
   };
 
@@ -47,7 +52,7 @@ class JTree {
   struct Collective {};
   template <typename GraphType>
   JTree(GraphType const& graph, std::vector<vid_t> const& seq, Collective, Options opts = Options()) {
-    if (!opts.isSupported())
+    if (!opts.isSupported() || opts.make_jxn)  // a rank's shard cannot give the union's widths
       throw std::invalid_argument("JTree: chordal-extension options are not built on MI355X");
     make_index(seq);
     graph.to_device();
@@ -137,5 +142,15 @@ class JTree {
                                    (uint32_t)seq.size(), parent.data(), pst.data()),
                   "JTree");
     jnodes.assign(parent, pst);
+    if (opts.make_jxn) {  // no width limit exists, so the tree is the one just built
+      std::vector<uint32_t> width(seq.size());
+      uint64_t facts[9];
+      sheep_check(sheep_tree_widths(graph.records_data(), graph.records(), seq.data(),
+                                    (uint32_t)seq.size(), parent.data(), pst.data(), width.data(),
+                                    facts),
+                  "JTree (widths)");
+      jnodes.makeKids();
+      jnodes.setWidths(std::move(width));
+    }
   }
 };

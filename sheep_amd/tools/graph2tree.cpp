@@ -68,7 +68,13 @@ int main(int argc, char* argv[]) {
     return 1;
   }
   if (!jopts.isSupported()) {
-    printf("ERROR: the chordal-extension options -k -e -j -w -x are not built in this version.\n");
+    printf("ERROR: of the chordal-extension options only -k -e -j together (exact widths) are built "
+           "in this version; -w and -x are not.\n");
+    return 1;
+  }
+  if (jopts.make_jxn && (use_mpi_sort || use_mpi_reduce)) {
+    printf("ERROR: -j needs the whole graph in one process: the widths of a shard's tree are not "
+           "the graph's.\n");
     return 1;
   }
   const char* graph_filename = argv[optind];
