@@ -300,8 +300,10 @@ int sheep_graph2tree_multi_local(const uint32_t* const* d_uv, const uint64_t* m,
  * with an edge needs one in [0, n_parts)); d_rank: n_ids positions in seq (sheep_sequence_dev).
  * out (host, 11 words): edges cut, Vcom vol, vertex balance (max), ECV(hash), its balance,
  * ECV(down), its balance, ECV(up), its balance, edges (adjacency entries / 2), nodes.
- * Synchronises.  -ERANGE: an id, part or position out of range; -EINVAL: n_parts outside
- * [1, 32768] or 2m >= 2^32. */
+ * Synchronises.  m == 0 gives eleven zeros.  -ERANGE: an id, part or position out of range;
+ * -EINVAL (answered before any device is touched): a null argument with m > 0, n_parts
+ * outside [1, 32768] or 2m >= 2^32; also a vertex with more adjacency entries than one
+ * id-range pass sorts (2^eval_pass, 2^31 unless the option lowers it). */
 int sheep_evaluate_dev(const uint32_t* d_uv, uint64_t m, const int16_t* d_parts,
                        const uint32_t* d_rank, uint32_t n_ids, uint32_t n_parts, uint64_t* out,
                        void* stream);
@@ -318,7 +320,10 @@ int sheep_evaluate(const uint32_t* edges_uv, uint64_t m, const int16_t* parts, u
  * pairs grouped by part, each part in the host writer's order (X ascending, then record
  * order); part_start (host, n_parts + 1) the first pair of each part (part_start[n_parts] = the
  * number written).  d_parts / d_rank: n_ids int16 parts and positions in seq.  Synchronises.
- * -ERANGE: an id outside the sequence, or an endpoint without a part in [0, n_parts). */
+ * -ERANGE: a record x != y with an id >= n_ids or outside the sequence, or with an endpoint
+ * (either one, as the writer asserts) without a part in [0, n_parts); a self-loop is skipped
+ * unread.  -EINVAL (before any device is touched): a null argument, n_parts outside
+ * [1, 32768] or m >= 2^32.  m == 0 gives part_start all zero. */
 int sheep_partition_edges_dev(const uint32_t* d_uv, uint64_t m, const int16_t* d_parts,
                               const uint32_t* d_rank, uint32_t n_ids, uint32_t n_parts,
                               uint32_t* d_out, uint64_t* part_start, void* stream);

@@ -346,6 +346,10 @@ static void require_endpoints(uint64_t m, const char* what) {
     throw ApiError(-EINVAL, std::string(what) + ": at most 2^31 - 1 records (u32 endpoint offsets)");
 }
 
+static void require_parts(uint32_t n_parts) {  // parts are int16 (part_t)
+  if (n_parts == 0 || n_parts > 32768) throw ApiError(-EINVAL, "n_parts must be in [1, 32768]");
+}
+
 static inline int bits_for(uint64_t v) {  // number of significant bits
   int b = 0;
   while (v) { ++b; v >>= 1; }
@@ -2160,7 +2164,6 @@ int sheep_graph2tree_dev(const uint32_t* d_uv, uint64_t m, uint32_t n_ids, int d
 static void evaluate_dev(Ctx& c, const uint32_t* d_uv, uint64_t m, const int16_t* d_parts,
                          const uint32_t* d_rank, uint32_t n_ids, uint32_t n_parts, uint64_t* out,
                          hipStream_t s) {
-  if (n_parts == 0 || n_parts > 32768) throw ApiError(-EINVAL, "n_parts must be in [1, 32768]");
   uint32_t* deg = (uint32_t*)c.scratch.get("deg", (size_t)std::max<uint32_t>(n_ids, 1) * 4);
   launch_degree(d_uv, m, n_ids, SHEEP_DEGREE_LLAMA, deg, nullptr, c.d_err, s);
   // Each metric sorts one key per adjacency entry (2m of them, less the self-loops' second).
@@ -2225,6 +2228,10 @@ int sheep_evaluate_dev(const uint32_t* d_uv, uint64_t m, const int16_t* d_parts,
                        const uint32_t* d_rank, uint32_t n_ids, uint32_t n_parts, uint64_t* out,
                        void* stream) {
   API_BEGIN
+  if (!out || (m && (!d_uv || !d_parts || !d_rank)))
+    throw ApiError(-EINVAL, "sheep_evaluate_dev: null argument");
+  require_parts(n_parts);
+  require_endpoints(m, "evaluate");  // one u64 key per adjacency entry, sorted by u32 offsets
   Ctx& c = ctx();
   require_aligned(d_uv, "d_uv");
   evaluate_dev(c, d_uv, m, d_parts, d_rank, n_ids, n_parts, out, pick(c, stream));
@@ -2234,8 +2241,6 @@ int sheep_evaluate_dev(const uint32_t* d_uv, uint64_t m, const int16_t* d_parts,
 static void partition_edges_dev(Ctx& c, const uint32_t* d_uv, uint64_t m, const int16_t* d_parts,
                                 const uint32_t* d_rank, uint32_t n_ids, uint32_t n_parts,
                                 uint32_t* d_out, uint64_t* part_start, hipStream_t s) {
-  require_records(m, "partition edges");
-  if (n_parts == 0 || n_parts > 32768) throw ApiError(-EINVAL, "n_parts must be in [1, 32768]");
   const uint64_t mm = std::max<uint64_t>(m, 1);
   uint64_t* items = (uint64_t*)c.scratch.get("e_items", mm * 8);
   uint64_t* items_b = (uint64_t*)c.scratch.get("e_items_b", mm * 8);
@@ -2786,6 +2791,10 @@ int sheep_partition_edges_dev(const uint32_t* d_uv, uint64_t m, const int16_t* d
                               const uint32_t* d_rank, uint32_t n_ids, uint32_t n_parts,
                               uint32_t* d_out, uint64_t* part_start, void* stream) {
   API_BEGIN
+  if (!part_start || (m && (!d_uv || !d_parts || !d_rank || !d_out)))
+    throw ApiError(-EINVAL, "sheep_partition_edges_dev: null argument");
+  require_parts(n_parts);
+  require_records(m, "partition edges");
   Ctx& c = ctx();
   require_aligned(d_uv, "d_uv");
   partition_edges_dev(c, d_uv, m, d_parts, d_rank, n_ids, n_parts, d_out, part_start, pick(c, stream));
@@ -2796,6 +2805,14 @@ int sheep_partition_edges(const uint32_t* edges_uv, uint64_t m, const int16_t* p
                           uint32_t n_parts_vid, const uint32_t* seq, uint32_t n_seq, uint32_t n_parts,
                           uint32_t* out_uv, uint64_t* part_start) {
   API_BEGIN
+  if (!part_start || (m && (!edges_uv || !out_uv)) || (n_parts_vid && !parts) || (n_seq && !seq))
+    throw ApiError(-EINVAL, "sheep_partition_edges: null argument");
+  require_parts(n_parts);
+  require_records(m, "partition edges");
+  if (m == 0 && n_seq == 0) {  // nothing to upload, nothing to write
+    std::fill(part_start, part_start + n_parts + 1, (uint64_t)0);
+    return SHEEP_OK;
+  }
   Ctx& c = ctx();
   hipStream_t s = c.stream;
   uint64_t top = n_parts_vid;  // 64-bit: an id 0xFFFFFFFF would wrap max id + 1 to 0
@@ -3201,6 +3218,14 @@ int sheep_degree_seq(const uint32_t* edges_uv, uint64_t m, uint32_t n_ids, int d
 int sheep_evaluate(const uint32_t* edges_uv, uint64_t m, const int16_t* parts, uint32_t n_parts_vid,
                    const uint32_t* seq, uint32_t n_seq, uint32_t n_parts, uint64_t* out) {
   API_BEGIN
+  if (!out || (m && !edges_uv) || (n_parts_vid && !parts) || (n_seq && !seq))
+    throw ApiError(-EINVAL, "sheep_evaluate: null argument");
+  require_parts(n_parts);
+  require_endpoints(m, "evaluate");
+  if (m == 0 && n_seq == 0) {  // no adjacency entry: nothing to upload, every number is 0
+    std::fill(out, out + 11, (uint64_t)0);
+    return SHEEP_OK;
+  }
   Ctx& c = ctx();
   hipStream_t s = c.stream;
   uint64_t top = n_parts_vid;  // 64-bit: an id 0xFFFFFFFF would wrap max id + 1 to 0

@@ -69,15 +69,19 @@ __global__ void k_ev_swap(uint64_t* keys, uint64_t n) {
   }
 }
 
-// Two keys per record (slot 2e: x -> y, slot 2e + 1: y -> x, or ~0 for a self-loop).
+// Two keys per record (slot 2e: x -> y, slot 2e + 1: y -> x, or ~0 for a self-loop).  A record
+// with an id >= n_ids gives ~0 twice and reads neither parts nor pos: k_ev_records raises
+// ERR_RANGE for it, but nobody reads the error word before this kernel runs.
 template <int METRIC>
-__global__ void k_ev_keys(const uint2* __restrict__ uv, uint64_t m, const int16_t* __restrict__ parts,
-                          const uint32_t* __restrict__ pos, uint64_t* __restrict__ keys) {
+__global__ void k_ev_keys(const uint2* __restrict__ uv, uint64_t m, uint32_t n_ids,
+                          const int16_t* __restrict__ parts, const uint32_t* __restrict__ pos,
+                          uint64_t* __restrict__ keys) {
   for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < m;
        e += (uint64_t)gridDim.x * blockDim.x) {
     const uint2 r = uv[e];
-    keys[2 * e] = ev_key<METRIC>(r.x, r.y, parts, pos);
-    keys[2 * e + 1] = r.x != r.y ? ev_key<METRIC>(r.y, r.x, parts, pos) : ~0ull;
+    const bool ok = r.x < n_ids && r.y < n_ids;
+    keys[2 * e] = ok ? ev_key<METRIC>(r.x, r.y, parts, pos) : ~0ull;
+    keys[2 * e + 1] = ok && r.x != r.y ? ev_key<METRIC>(r.y, r.x, parts, pos) : ~0ull;
   }
 }
 
@@ -86,7 +90,7 @@ __global__ void k_ev_keys(const uint2* __restrict__ uv, uint64_t m, const int16_
 // caller filled keys with ~0 up to the pass's bound.  Distinct keys of different passes differ
 // in X, so the passes' distinct counts add up.
 template <int METRIC>
-__global__ void k_ev_keys_range(const uint2* __restrict__ uv, uint64_t m,
+__global__ void k_ev_keys_range(const uint2* __restrict__ uv, uint64_t m, uint32_t n_ids,
                                 const int16_t* __restrict__ parts, const uint32_t* __restrict__ pos,
                                 uint32_t v0, uint32_t v1, uint64_t* __restrict__ keys,
                                 unsigned long long* n_out) {
@@ -97,8 +101,12 @@ __global__ void k_ev_keys_range(const uint2* __restrict__ uv, uint64_t m,
     uint64_t k0 = ~0ull, k1 = ~0ull;
     if (e < m) {
       const uint2 r = uv[e];
-      if (r.x >= v0 && r.x < v1) k0 = ev_key<METRIC>(r.x, r.y, parts, pos);
-      if (r.x != r.y && r.y >= v0 && r.y < v1) k1 = ev_key<METRIC>(r.y, r.x, parts, pos);
+      // [v0, v1) bounds one endpoint only; the other is held to n_ids as in k_ev_keys.  The
+      // caller reaches the passes only after check_err saw the degree pass accept every id,
+      // so this guard never fires there: it keeps the two key kernels alike.
+      const bool ok = r.x < n_ids && r.y < n_ids;
+      if (ok && r.x >= v0 && r.x < v1) k0 = ev_key<METRIC>(r.x, r.y, parts, pos);
+      if (ok && r.x != r.y && r.y >= v0 && r.y < v1) k1 = ev_key<METRIC>(r.y, r.x, parts, pos);
     }
     const uint32_t c = (k0 != ~0ull) + (k1 != ~0ull);
     uint32_t inc = c;
@@ -239,8 +247,8 @@ void launch_evaluate(const uint32_t* uv, uint64_t m, const int16_t* parts, const
                 : metric == EV_DOWN ? k_ev_keys_range<EV_DOWN> : k_ev_keys_range<EV_UP>;
         (void)hipMemsetAsync(keys, 0xFF, n * 8, s);
         (void)hipMemsetAsync(nk, 0, 8, s);
-        hipLaunchKernelGGL(kk, dim3(ev_grid(m)), dim3(EV_BLOCK), 0, s, (const uint2*)uv, m, parts,
-                           pos, v0, v1, keys, nk);
+        hipLaunchKernelGGL(kk, dim3(ev_grid(m)), dim3(EV_BLOCK), 0, s, (const uint2*)uv, m, n_ids,
+                           parts, pos, v0, v1, keys, nk);
         uint64_t* by_part = radix_sort_u64(keys, keys_b, keys, n, 0, 16, rtmp, s);
         uint64_t* other = by_part == keys ? keys_b : keys;
         hipLaunchKernelGGL(k_ev_swap, dim3(ev_grid(n)), dim3(EV_BLOCK), 0, s, by_part, n);
@@ -255,8 +263,8 @@ void launch_evaluate(const uint32_t* uv, uint64_t m, const int16_t* parts, const
     auto kk = metric == EV_VCOM ? k_ev_keys<EV_VCOM>
             : metric == EV_HASH ? k_ev_keys<EV_HASH>
             : metric == EV_DOWN ? k_ev_keys<EV_DOWN> : k_ev_keys<EV_UP>;
-    hipLaunchKernelGGL(kk, dim3(ev_grid(m)), dim3(EV_BLOCK), 0, s, (const uint2*)uv, m, parts, pos,
-                       keys);
+    hipLaunchKernelGGL(kk, dim3(ev_grid(m)), dim3(EV_BLOCK), 0, s, (const uint2*)uv, m, n_ids, parts,
+                       pos, keys);
     uint64_t* by_part = radix_sort_u64(keys, keys_b, keys, n, 0, 16, rtmp, s);
     uint64_t* other = by_part == keys ? keys_b : keys;
     hipLaunchKernelGGL(k_ev_swap, dim3(ev_grid(n)), dim3(EV_BLOCK), 0, s, by_part, n);
@@ -289,16 +297,22 @@ __global__ void k_pe_part_keys(const uint64_t* __restrict__ sorted, uint64_t m,
        j += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t it = sorted[j];
     const uint32_t i = (uint32_t)it;
-    uint32_t p = n_parts;  // self-loops: after every part
-    if ((uint32_t)(it >> 32) != n_ids) {
-      const uint2 e = uv[i];
+    uint32_t p = n_parts;  // self-loops and refused records: after every part
+    const uint2 e = uv[i];  // (not the sorted key: an id n_ids out of range looks like a self-loop's)
+    if (e.x != e.y) {
       const uint32_t x = min(e.x, e.y), y = max(e.x, e.y);
-      if (y >= n_ids) { atomicOr(err, ERR_RANGE); continue; }
-      const int16_t q = pos[x] < pos[y] ? parts[x] : parts[y];
-      if (q < 0 || (uint32_t)q >= n_parts) atomicOr(err, ERR_RANGE);  // a vertex without a part
-      else p = (uint32_t)q;
+      bool ok = y < n_ids;
+      if (ok) {
+        // both endpoints in the sequence and with a part, as the writer asserts of both
+        const uint32_t px = pos[x], py = pos[y];
+        const int16_t qx = parts[x], qy = parts[y];
+        ok = px != INV && py != INV && qx >= 0 && (uint32_t)qx < n_parts && qy >= 0 &&
+             (uint32_t)qy < n_parts;
+        if (ok) p = (uint32_t)(px < py ? qx : qy);
+      }
+      if (!ok) atomicOr(err, ERR_RANGE);
     }
-    items[j] = ((uint64_t)p << 32) | i;
+    items[j] = ((uint64_t)p << 32) | i;  // always written: the next sort reads every slot
   }
 }
 

@@ -190,6 +190,20 @@ def evaluate(uv, parts, rank, n_parts=None):
     return dict(zip(EVAL_KEYS, (int(x) for x in out)))
 
 
+def partition_edges(uv, parts, rank, n_parts):
+    """graph2tree -p K -o OUT's edge output on the GPU (sheep_partition_edges_dev): ``parts``
+    int16 and ``rank`` positions per vertex id (cuda).  Returns (the (m, 2) uint32 tensor of
+    pairs grouped by part, part_start as n_parts + 1 numpy uint64)."""
+    import numpy as np
+
+    m = uv.shape[0]
+    out = torch.empty((max(m, 1), 2), dtype=torch.uint32, device=uv.device)
+    start = np.zeros(n_parts + 1, np.uint64)
+    capi.call("sheep_partition_edges_dev", _p(uv), m, _p(parts), _p(rank), parts.numel(),
+              n_parts, _p(out), ctypes.c_void_p(start.ctypes.data), _stream())
+    return out, start
+
+
 FACT_KEYS = capi.FACT_KEYS
 report_dict = capi.report_dict
 
