@@ -33,6 +33,7 @@
  * changed.  ABI 1.2 adds sheep_read_net_dev and sheep_records_load_net (SNAP text parsed on the
  * device) and the option net_chunk; nothing else changed.  ABI 1.3 adds sheep_tree_widths_dev
  * and sheep_tree_widths (the exact width of every bag, without storing a bag); nothing else
+ * changed.  ABI 1.4 adds sheep_partition_dev (forwardPartition of a tree in HBM); nothing else
  * changed.
  */
 #ifndef SHEEP_AMD_H
@@ -422,6 +423,23 @@ int sheep_powerlaw_dev(uint32_t* d_uv, uint32_t n, double gamma, double i0, uint
 int sheep_partition(const uint32_t* parent, const uint32_t* pst, uint32_t n_seq,
                     const uint32_t* seq, const int32_t* ks, uint32_t n_k, double balance,
                     int16_t* parts_out, uint32_t n_vid, uint32_t* created_out);
+
+/* ---- forward partition of a tree in HBM (ABI 1.4) -------------------------------------------
+ * sheep_partition with the tree where sheep_graph2tree_dev leaves it: d_parent, d_pst, d_seq are
+ * device arrays of n_seq entries, d_parts a device array of n_k * n_vid int16 (vid-indexed, -1
+ * for ids outside seq, ready for sheep_evaluate_dev / sheep_partition_edges_dev); ks and
+ * created_out (nullable) are host arrays.  The same parts and counts as sheep_partition, bit for
+ * bit: pst weights, one table for all k in turn.  Every pass over all ranks is a kernel (subtree
+ * sums and the push-down of the parts as prefix sums over the Euler tour, whatever the height or
+ * the fan-out); the host packs only the ranks whose subtree outweighs a part.
+ * -EINVAL (before any device is touched): a null argument, n_seq == 0, a k outside [1, 32767];
+ * -EINVAL: n_seq >= 2^31, a forest not in heap order, a rank whose pst exceeds
+ * total / k * balance (rows of earlier k are written); -ERANGE: a seq id >= n_vid (nothing is
+ * written), more than 32767 bins.  Phase times through sheep_last_timings (part_tour,
+ * part_sums, then part_heavy, part_host, part_push per k).  Synchronises the stream. */
+int sheep_partition_dev(const uint32_t* d_parent, const uint32_t* d_pst, uint32_t n_seq,
+                        const uint32_t* d_seq, const int32_t* ks, uint32_t n_k, double balance,
+                        int16_t* d_parts, uint32_t n_vid, uint32_t* created_out, void* stream);
 
 /* Kernel timing of the last synchronising call (ms per named phase), for bench/profiling.
  * Fills up to cap (name, ms) pairs; returns the count. */

@@ -222,7 +222,7 @@ def graph2tree(uv, mode=DEGREE_LLAMA):
     return seq, build_tree(uv, seq)
 
 
-# ---- partition (host, as in the reference) ---------------------------------------------------
+# ---- partition (host, as in the reference; partition_dev: the tree stays in HBM) -------------
 
 def partition(tree, seq, ks, balance=1.03):
     """Partition(seq, jnodes, k, balance) (partition.cpp:50-67 -> forwardPartition :86-157) for
@@ -236,6 +236,28 @@ def partition(tree, seq, ks, balance=1.03):
     capi.call("sheep_partition", _ptr(tree.parent), _ptr(tree.pst), tree.size(), _ptr(seq),
               _ptr(ks), ks.size, float(balance), _ptr(parts), n_vid, _ptr(created))
     return [parts[i, :n_vid] for i in range(ks.size)], [int(c) for c in created]
+
+
+def partition_dev(parent, pst, seq, ks, balance=1.03, n_seq=None, n_vid=None):
+    """partition() for a tree in HBM (sheep_partition_dev): ``parent``, ``pst`` and ``seq`` are
+    cuda uint32 tensors as sheep_amd.device.graph2tree leaves them (their first ``n_seq`` entries
+    count; default: all).  Every k of ``ks`` runs in one call on one table.  Returns a
+    (len(ks), n_vid) int16 cuda tensor, vid-indexed with -1 for ids not in seq (``n_vid``
+    defaults to max(seq) + 1), and the created part counts: bit for bit what partition() gives."""
+    import torch
+
+    ks = np.ascontiguousarray(np.atleast_1d(ks), np.int32)
+    n = int(parent.numel()) if n_seq is None else int(n_seq)
+    if n_vid is None:
+        n_vid = int((seq[:n].view(torch.int32).to(torch.int64) & 0xFFFFFFFF).max().item()) + 1 \
+            if n else 0
+    parts = torch.empty((ks.size, max(int(n_vid), 1)), dtype=torch.int16, device=parent.device)
+    created = np.zeros(max(ks.size, 1), np.uint32)
+    capi.call("sheep_partition_dev", ctypes.c_void_p(parent.data_ptr()),
+              ctypes.c_void_p(pst.data_ptr()), n, ctypes.c_void_p(seq.data_ptr()), _ptr(ks),
+              ks.size, float(balance), ctypes.c_void_p(parts.data_ptr()), int(n_vid),
+              _ptr(created), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return parts[:, :int(n_vid)], [int(c) for c in created[:ks.size]]
 
 
 # ---- multi-rank (graph2tree -i -r; a communicator from sheep_comm_init on every rank) ---------

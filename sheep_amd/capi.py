@@ -117,6 +117,8 @@ def lib():
         "sheep_tree_widths": [u32p, c.c_uint64, u32p, c.c_uint32, u32p, u32p, u32p, vp],
         "sheep_partition": [u32p, u32p, c.c_uint32, u32p, vp, c.c_uint32, c.c_double, vp,
                             c.c_uint32, vp],
+        "sheep_partition_dev": [u32p, u32p, c.c_uint32, u32p, vp, c.c_uint32, c.c_double, vp,
+                                c.c_uint32, vp, vp],
     }
     for name, args in sigs.items():
         f = getattr(L, name)

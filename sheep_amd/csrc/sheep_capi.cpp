@@ -26,6 +26,7 @@
 #include "net_layout.h"
 #include "verify_layout.h"
 #include "width_layout.h"
+#include "part_layout.h"
 
 namespace sheep {
 
@@ -172,6 +173,7 @@ static void ctx_teardown(Ctx& c) {
   c.ev_pool.clear();
   (void)hipHostFree(c.h_bstart);
   if (c.h_chunks) (void)hipHostFree(c.h_chunks);
+  if (c.h_part) (void)hipHostFree(c.h_part);
   (void)hipFree(c.d_err);
   (void)hipHostFree(c.h_pinned);
 }
@@ -1979,7 +1981,8 @@ extern "C" {
 
 // 1.1: sheep_verify_tree*, sheep_tree_facts_dev; 1.2: sheep_read_net_dev, sheep_records_load_net;
 // 1.3: sheep_tree_widths*
-int sheep_abi_version(void) { return (1 << 16) | 3; }
+// 1.4: sheep_partition_dev
+int sheep_abi_version(void) { return (1 << 16) | 4; }
 
 const char* sheep_last_error(void) { return g_last_error.c_str(); }
 
@@ -2440,6 +2443,128 @@ int sheep_tree_widths_dev(const uint32_t* d_uv, uint64_t m, const uint32_t* d_ra
   Ctx& c = ctx();
   require_aligned(d_uv, "d_uv");
   tree_widths_dev(c, d_uv, m, d_rank, n_ids, n_seq, d_parent, d_pst, d_width, out, pick(c, stream));
+  API_END
+}
+
+// ---- forward partition of a tree in HBM (sheep_part.hip, part_layout.h) ---------------------
+
+// The context's pinned staging for the heavy ranks (grown on demand).
+static void* part_pinned(Ctx& c, size_t bytes) {
+  if (c.h_part_bytes < bytes) {
+    if (c.h_part) HIP_CHECK(hipHostFree(c.h_part));
+    c.h_part = nullptr;
+    c.h_part_bytes = 0;
+    HIP_CHECK(hipHostMalloc(&c.h_part, bytes, hipHostMallocDefault));
+    c.h_part_bytes = bytes;
+  }
+  return c.h_part;
+}
+
+static void partition_dev(Ctx& c, const uint32_t* d_parent, const uint32_t* d_pst, uint32_t n_seq,
+                          const uint32_t* d_seq, const int32_t* ks, uint32_t n_k, double balance,
+                          int16_t* d_parts, uint32_t n_vid, uint32_t* created_out, hipStream_t s) {
+  Scratch& sc = c.scratch;
+  Timer tm(s);
+  unsigned long long* vws;
+  const std::vector<unsigned long long> h = vf_heap(c, d_parent, n_seq, &vws, s);
+  if (h[VF_HEAP]) throw ApiError(-EINVAL, "sheep_partition_dev: forest not heap-ordered");
+  unsigned long long* ws = (unsigned long long*)sc.get("pt_ws", PT_WS_WORDS * 8);
+  launch_pt_reduce(d_pst, d_seq, n_seq, ws, s);
+  const VfTour T = vf_tour(c, d_parent, n_seq, s);
+  unsigned long long w[PT_WS_WORDS];
+  uint32_t rslots[2];  // the virtual parent's children list: the roots
+  HIP_CHECK(hipMemcpyAsync(w, ws, sizeof w, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(&rslots[0], T.kfirst + n_seq, 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(&rslots[1], T.klast + n_seq, 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  tm.mark("part_tour");
+  if (w[PT_SEQMAX] >= n_vid) throw ApiError(-ERANGE, "sheep_partition_dev: n_vid < max(seq) + 1");
+  const size_t total = (size_t)w[PT_TOTAL], wmax = (size_t)w[PT_WMAX];
+
+  long long* sums = (long long*)sc.get("vf_scan_sums", vf_scan_tiles(n_seq) * 8);
+  long long* wt = (long long*)T.cells_a;  // free once the tour is done
+  unsigned long long* s0 = (unsigned long long*)sc.get("pt_s0", (size_t)n_seq * 8);
+  unsigned long long* ks0 = (unsigned long long*)sc.get("pt_ks0", (size_t)n_seq * 8);
+  launch_pt_sums(T, d_pst, wt, sums, s0, ks0, s);
+  // Slots [a, b] of the children lists with their subtree sums: two plain copies.
+  std::vector<uint64_t> items, vals;
+  auto fetch = [&](uint32_t a, uint32_t b, std::vector<PtKid>& out) {
+    if (a == VF_NONE || b < a || b >= n_seq) throw ApiError(-EIO, "sheep_partition_dev: bad kids slots");
+    const size_t cnt = (size_t)(b - a) + 1;
+    items.resize(cnt);
+    vals.resize(cnt);
+    HIP_CHECK(hipMemcpyAsync(items.data(), T.kids + a, cnt * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(vals.data(), ks0 + a, cnt * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    out.reserve(out.size() + cnt);
+    for (size_t i = 0; i < cnt; ++i) out.push_back({vf_kid(items[i]), vals[i]});
+  };
+  std::vector<PtKid> roots;
+  fetch(rslots[0], rslots[1], roots);  // (a forest of n_seq >= 1 ranks has a root)
+  tm.mark("part_sums");
+
+  uint32_t* flag = (uint32_t*)sc.get("pt_flag", ((size_t)n_seq + 1) * 4);
+  uint32_t* idx = (uint32_t*)sc.get("pt_idx", ((size_t)n_seq + 1) * 4);
+  uint32_t* stmp = (uint32_t*)sc.get("pt_scan_tmp", scan_tmp_words((uint64_t)n_seq + 1) * 4);
+  PtOrders orders;  // one table for every k
+  PtOut out;
+  for (uint32_t i = 0; i < n_k; ++i) {
+    // A vertex heavier than a part never fits (sheep_partition refuses it the same way).
+    const size_t max_component = pt_max_component(total, (int16_t)ks[i], balance);
+    if (wmax > max_component) {
+      (void)hipStreamSynchronize(s);  // the rows of the earlier k
+      throw ApiError(-EINVAL, "sheep_partition_dev: a vertex's pst weight exceeds total/k*balance");
+    }
+    launch_pt_flag(s0, n_seq, max_component, flag, idx, stmp, s);
+    HIP_CHECK(hipMemcpyAsync(c.h_pinned + 4, idx + n_seq, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const uint32_t nh = c.h_pinned[4];
+    const PtHeavy* H = nullptr;
+    if (nh) {
+      PtHeavy* dH = (PtHeavy*)sc.get("pt_heavy", (size_t)nh * sizeof(PtHeavy));
+      launch_pt_heavy(flag, idx, d_parent, s0, T, nh, dH, s);
+      H = (const PtHeavy*)part_pinned(c, (size_t)nh * sizeof(PtHeavy));
+      HIP_CHECK(hipMemcpyAsync((void*)H, dH, (size_t)nh * sizeof(PtHeavy), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+    tm.mark("part_heavy");
+    if (pt_partition(H, nh, roots.data(), roots.size(), max_component, orders, fetch, out)) {
+      (void)hipStreamSynchronize(s);
+      throw ApiError(-ERANGE, "sheep_partition_dev: more than 32767 parts");
+    }
+    const uint32_t nd = (uint32_t)out.deltas.size();
+    PtDelta* dD = (PtDelta*)sc.get("pt_deltas", (size_t)nd * sizeof(PtDelta));
+    if (nd) {
+      HIP_CHECK(hipMemcpyAsync(dD, out.deltas.data(), (size_t)nd * sizeof(PtDelta),
+                               hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipStreamSynchronize(s));  // out is reused by the next k
+    }
+    tm.mark("part_host");
+    launch_pt_push(dD, nd, T, wt, sums, d_seq, n_vid, d_parts + (size_t)i * n_vid, c.d_err, s);
+    tm.mark("part_push");
+    if (created_out) created_out[i] = out.created;
+    // counts, not times: |H|, cut ranks, kids fetched at this k
+    tm.host_ms("part_H", (double)nh);
+    tm.host_ms("part_cuts", (double)out.cuts);
+    tm.host_ms("part_kids", (double)out.kids_fetched);
+  }
+  check_err(c, s);  // synchronises
+  tm.finish(c);
+}
+
+int sheep_partition_dev(const uint32_t* d_parent, const uint32_t* d_pst, uint32_t n_seq,
+                        const uint32_t* d_seq, const int32_t* ks, uint32_t n_k, double balance,
+                        int16_t* d_parts, uint32_t n_vid, uint32_t* created_out, void* stream) {
+  API_BEGIN
+  if (n_seq == 0 || !d_parent || !d_pst || !d_seq || !ks || !d_parts)
+    throw ApiError(-EINVAL, "sheep_partition_dev: empty tree or null argument");
+  for (uint32_t i = 0; i < n_k; ++i)
+    if (ks[i] < 1 || ks[i] > 32767)
+      throw ApiError(-EINVAL, "sheep_partition_dev: k outside [1, 32767]");
+  if (n_k == 0) return SHEEP_OK;
+  Ctx& c = ctx();
+  partition_dev(c, d_parent, d_pst, n_seq, d_seq, ks, n_k, balance, d_parts, n_vid, created_out,
+                pick(c, stream));
   API_END
 }
 

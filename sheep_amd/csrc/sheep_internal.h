@@ -99,6 +99,8 @@ struct Ctx {
   // and their device copies: host-pointer calls on them upload nothing
   struct Registered { const uint32_t* host; uint64_t m; uint32_t* dev; };
   std::vector<Registered> registered;
+  void* h_part = nullptr;  // pinned: the heavy ranks and the deltas of sheep_partition_dev
+  size_t h_part_bytes = 0;
 };
 
 Ctx& ctx();  // this thread's context for the current device (sheep_gpu_init)
@@ -462,6 +464,30 @@ void launch_tw_weights(const uint64_t* keys, uint64_t m, const VfTour& T, const 
 // From the scanned weights S: width_out (n, nullable), ws[TW_WIDTH .. TW_HALO].
 void launch_tw_final(const VfTour& T, const uint32_t* pst, const long long* S, uint32_t* width_out,
                      unsigned long long* ws, hipStream_t s);
+// Forward partition of a tree in HBM (sheep_part.hip; the host half in part_layout.h).  The
+// counter words (ws: PT_WS_WORDS u64, reset by launch_pt_reduce): sum and maximum of pst, maximum
+// of seq.
+enum { PT_TOTAL = 0, PT_WMAX, PT_SEQMAX, PT_WS_WORDS = 8 };
+struct PtHeavy;  // part_layout.h
+struct PtDelta;
+void launch_pt_reduce(const uint32_t* pst, const uint32_t* seq, uint32_t n, unsigned long long* ws,
+                      hipStream_t s);
+// s0 (n u64): the subtree sum of pst per rank; ks0 (n u64): the same in children-list slot order
+// (ks0[i] belongs to the kid in T.kids[i]).  wt: 2n i64 scratch; sums: vf_scan_tiles(n) i64.
+void launch_pt_sums(const VfTour& T, const uint32_t* pst, long long* wt, long long* sums,
+                    unsigned long long* s0, unsigned long long* ks0, hipStream_t s);
+// flag / idx (n + 1 u32 each): s0[v] > max_component and its exclusive scan, idx[n] = |H|; tmp:
+// scan_tmp_words(n + 1) u32.
+void launch_pt_flag(const unsigned long long* s0, uint32_t n, uint64_t max_component, uint32_t* flag,
+                    uint32_t* idx, uint32_t* tmp, hipStream_t s);
+// out (nh records): the heavy ranks ascending, each with its parent's index in H.
+void launch_pt_heavy(const uint32_t* flag, const uint32_t* idx, const uint32_t* parent,
+                     const unsigned long long* s0, const VfTour& T, uint32_t nh, PtHeavy* out,
+                     hipStream_t s);
+// row (n_vid int16) = -1, then row[seq[v]] = the part of v's nearest packed ancestor-or-self from
+// the nd deltas (wt: 2n i64 scratch).  ERR_RANGE for a seq id >= n_vid (nothing is stored for it).
+void launch_pt_push(const PtDelta* deltas, uint32_t nd, const VfTour& T, long long* wt, long long* sums,
+                    const uint32_t* seq, uint32_t n_vid, int16_t* row, uint32_t* err, hipStream_t s);
 // XS1 records {u32 tail, u32 head, f32 weight} -> (tail, head) pairs; max id + 1 into *max_id.
 void launch_strip_xs1(const uint32_t* raw, uint64_t n, uint32_t* uv, uint32_t* max_id, hipStream_t s);
 // One chunk of SNAP text (sheep_ingest.hip; net_layout.h): n bytes at text (allocated up to a

@@ -7,7 +7,16 @@
 // Parity note: forwardPartition orders kids with the unstable std::sort (partition.cpp:104)
 // IN PLACE on the table's kids lists, and partition_tree reuses one table for every k, so the
 // same libstdc++ std::sort is called here on the same ranges in the same order.
+//
+// Partition::on_device (not in the reference) runs forwardPartition for a whole k list on the GPU
+// (sheep_partition_dev): the tree goes to HBM once, and only the ranks whose subtree outweighs a
+// part come back to the host for the packing.  The parts are the host's, bit for bit.
 #pragma once
+#ifndef __HIP_PLATFORM_AMD__
+#define __HIP_PLATFORM_AMD__ 1
+#endif
+#include <hip/hip_runtime_api.h>
+
 #include <algorithm>
 #include <atomic>
 #include <charconv>
@@ -47,6 +56,50 @@ class Partition {
     std::vector<part_t> tmp(*std::max_element(seq.cbegin(), seq.cend()) + 1, INVALID_PART);
     for (size_t i = 0; i != seq.size(); ++i) tmp.at(seq.at(i)) = parts.at(i);
     parts = std::move(tmp);
+  }
+
+  // Partition(seq, jnodes, np, balance_factor) with pst weights for every np of nps in turn, on
+  // the GPU and in ONE call, so that the kids orders one k leaves behind are the next k's start
+  // as they are on one host table (partition_tree -P).  Uploads parent, pst_weight and seq,
+  // downloads the parts; the table's own kids lists stay as they are.
+  static std::vector<Partition> on_device(std::vector<vid_t> const& seq, JNodeTable const& jnodes,
+                                          std::vector<part_t> const& nps, double balance_factor = 1.03) {
+    if (seq.size() != jnodes.size() || seq.empty())
+      throw std::invalid_argument("Partition::on_device: sequence and tree of different sizes, or empty");
+    const size_t n = seq.size(), n_k = nps.size();
+    const size_t n_vid = (size_t)*std::max_element(seq.cbegin(), seq.cend()) + 1;
+    std::vector<uint32_t> host(3 * n);  // parent, pst, seq
+    for (jnid_t id = 0; id != n; ++id) {
+      host[id] = jnodes.parent(id);
+      host[n + id] = jnodes.pst_weight(id);
+      host[2 * n + id] = seq[id];
+    }
+    std::vector<int32_t> ks(nps.cbegin(), nps.cend());
+    struct DevBuf {
+      void* p = nullptr;
+      explicit DevBuf(size_t bytes) {
+        if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) throw std::bad_alloc();
+      }
+      ~DevBuf() { (void)hipFree(p); }
+    };
+    DevBuf tree(3 * n * sizeof(uint32_t)), dparts(n_k * n_vid * sizeof(part_t));
+    if (hipMemcpy(tree.p, host.data(), 3 * n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+      throw std::runtime_error("Partition::on_device: upload failed");
+    const uint32_t* d = (const uint32_t*)tree.p;
+    std::vector<uint32_t> created(n_k);
+    sheep_check(sheep_partition_dev(d, d + n, (uint32_t)n, d + 2 * n, ks.data(), (uint32_t)n_k,
+                                    balance_factor, (int16_t*)dparts.p, (uint32_t)n_vid, created.data(),
+                                    nullptr),
+                "Partition::on_device");
+    std::vector<Partition> out(n_k);
+    for (size_t i = 0; i != n_k; ++i) {
+      out[i].num_parts = nps[i];
+      out[i].parts.resize(n_vid);
+      if (hipMemcpy(out[i].parts.data(), (part_t const*)dparts.p + i * n_vid, n_vid * sizeof(part_t),
+                    hipMemcpyDeviceToHost) != hipSuccess)
+        throw std::runtime_error("Partition::on_device: download failed");
+    }
+    return out;
   }
 
   static size_t weight(JNodeTable const& jn, jnid_t id, bool vtx, bool pst) {  // partition.cpp:38-48
